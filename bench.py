@@ -2,7 +2,7 @@
 """bench.py — the reference's headline benchmark on the MI355X backend: llama-bench tg128 (+ pp512) for
 Llama-3-8B Q4_K_M (BASELINE.json configs[1]) on synthetic weights of that architecture.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 A "step" is one decoded token through the whole hot path (225 quantized mat-vecs + the element ops of
 llm_build_llama), driven with llama-bench's protocol (tools/llama-bench/llama-bench.cpp:1791-1810: one
@@ -13,14 +13,20 @@ N = 1 : the single-GPU configuration the metric is quoted on.
 N > 1 : `-sm layer` split, one process per GPU, activations handed over by RCCL send/recv (layer_split.py);
         N independent sequences are kept in flight so that every stage is busy (weak scaling).
 
-Rank 0 prints ONE JSON line: the contract fields + `roofline` (dominant kernel: the quantized mat-vec, HBM-bound,
-timed live with HIP events on the backend's own stream) + `cpu_baseline` (the oracle's CPU restatement of the
-same mat-vec work on the host cores, a bounded sample).
+Rank 0 prints ONE JSON line. A plain run sets up, warms up, times the K steps and prints the contract fields; `roofline` and
+`cpu_baseline` are null. `--full` adds everything measured beside the headline: `roofline` (dominant kernel: the quantized
+mat-vec, HBM-bound, timed live with HIP events on the backend's own stream), `cpu_baseline` (the oracle's CPU restatement of
+the same mat-vec work on the host cores, a bounded sample), the prompt pass (`--pp`), kernel / graph counters, the HBM read
+probe, the checker leg (`--parity`) and, for N > 1, the per-stage clocks, hand-off latencies and the one-sequence chain rate.
+
+--dump-outputs DIR: after the timed steps, the logits the last timed step handed back (what llama_get_logits returns) are
+written to DIR/logits.npy (float32); with the same arguments the inputs (weights, token ids) are the same from run to run.
 """
 import argparse
 import json
 import os
 import sys
+import tempfile
 import time
 from pathlib import Path
 
@@ -71,10 +77,10 @@ def cpu_baseline(model_cfg, ftype, budget_s=20.0):
     """Time the oracle (CPU restatement, OpenMP) on the same mat-vec work: a bounded sample of layers + the lm_head."""
     sys.path.insert(0, str(ROOT / "oracle"))
     import oracle as orc
-    native = orc.build(native=True, out_dir=Path(os.environ.get("TMPDIR", "/tmp")))
     cores = orc.cpu_budget(cap=64)          # affinity mask / cgroup quota, at most 64 threads (a GPU box shares a 256-thread host)
     os.environ["OMP_NUM_THREADS"] = str(cores)
-    L = orc.lib(native)
+    with tempfile.TemporaryDirectory() as tmp:     # a private build: a fixed name in the temp directory may be another user's or another version's
+        L = orc.lib(orc.build(native=True, out_dir=Path(tmp)))
     rng = np.random.default_rng(0)
     c = model_cfg
     assert ftype == "Q4_K_M"
@@ -122,6 +128,14 @@ def cpu_baseline(model_cfg, ftype, budget_s=20.0):
 
 
 
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: one DIR/<name>.npy (float32) per array the timed path returned in its last step"""
+    d = Path(out_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(d / f"{name}.npy", np.asarray(a, dtype=np.float32))
+
+
 def roofline_from_profile(prof):
     """the dominant kernel's achieved HBM rate from the backend's per-dispatch timings (option "profile": each grouped mat-vec dispatch carries its own
     start/stop event pair = the interval rocprofv3's kernel trace reports)"""
@@ -158,14 +172,21 @@ def main():
                     "registry (csrc/backend.cpp: the split buffer type); on a one-GPU box set GGML_MI355X_VIRTUAL_DEVICES to list the GPU several times")
     ap.add_argument("--gguf", default=None, help="run the same protocol on a model read from this GGUF file (llama / gpt-oss architectures) instead of the "
                     "synthetic weights of --model / --ftype")
-    ap.add_argument("--pp", type=int, default=512, help="prompt length for the extra pp measurement (0 = skip)")
+    ap.add_argument("--pp", type=int, default=512, help="prompt length for the extra pp measurement of --full (0 = skip)")
     ap.add_argument("--fa", type=int, default=0, help="1 = llama-bench -fa 1: FLASH_ATTN_EXT, V cache not transposed, n_kv padded to 256")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-profile", action="store_true")
-    ap.add_argument("--parity", action="store_true", help="also run the checker leg: perplexity statistics against the oracle on the small synthetic model, or on "
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the cpu_baseline leg")
+    ap.add_argument("--no-profile", action="store_true", help="--full without the roofline leg")
+    ap.add_argument("--parity", action="store_true", help="with --full: also run the checker leg: perplexity statistics against the oracle on the small synthetic model, or on "
                                                            "the --gguf model (its launches use the same kernel templates: keep it out of a run whose rocprofv3 summary is read per kernel)")
     ap.add_argument("--parity-positions", type=int, default=8192)
+    ap.add_argument("--full", action="store_true", help="besides the headline: roofline, cpu_baseline, the prompt pass, counters, the HBM read probe, "
+                    "--parity, and for N > 1 the per-stage clocks, hand-off latencies and the one-sequence chain")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the logits of the last timed step to DIR/logits.npy (float32)")
     args = ap.parse_args()
+    if args.parity and not args.full:
+        ap.error("--parity is a leg of --full: give both")
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     rank = int(os.environ.get("RANK", "0")); world = int(os.environ.get("WORLD_SIZE", "1")); local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     if world != args.gpus:
@@ -252,8 +273,10 @@ def main():
     result = {}
     if world == 1:
         def run_tokens(n):
+            out = None
             for i in range(n):
-                m.decode(tokens[i:i + 1], want_host=True, sync=True, view=True)     # llama_decode + llama_synchronize per token; the logits land in the pinned output buffer (llama_get_logits' view)
+                out = m.decode(tokens[i:i + 1], want_host=True, sync=True, view=True)     # llama_decode + llama_synchronize per token; the logits land in the pinned output buffer (llama_get_logits' view)
+            return out
         # warm-up: builds the graphs for every n_kv bucket and lets the backend capture them
         done = 0
         while done < W:
@@ -265,89 +288,94 @@ def main():
         import gc
         gc.collect(); gc.disable()
         sync_all(); t0 = time.perf_counter()
-        run_tokens(K)
+        logits = run_tokens(K)
         sync_all(); dt = time.perf_counter() - t0
         gc.enable()
-        cnt = be.counters()
         tok_s = K / dt
         result.update(value=tok_s, ms_per_step=dt / K * 1e3)
-        extra = {"graph_replays": cnt["graph_replays"], "kernels_per_token": None, "graph_nodes": m.graph_nodes(1),
-                 "weight_GB_per_token": m.weight_bytes / 1e9,
-                 "hbm_frac_whole_token": (m.weight_bytes * tok_s / 1e9) / HBM_PEAK_GBPS}
-        # kernel count per token from one eager token
-        be.set_option("graphs", 0); m.kv_clear(); be.reset_counters(); run_tokens(1)
-        extra["kernels_per_token"] = be.counters()["kernels_launched"]
-        be.set_option("graphs", 1)
-
-        roof = None
-        if not args.no_profile and args.row_split <= 1:      # (the per-device launches of a row split are not bracketed: that mode reports throughput only)
-            # dominant kernel, timed live with HIP events on the backend stream. Option "profile" = 1: eager launches, each grouped mat-vec
-            # dispatch carrying its own start/stop event pair (hipExtLaunchKernelGGL), i.e. kernel start -> kernel end by the packet's
-            # timestamps, the same interval rocprofv3's kernel trace reports (round 1 recorded an event either side of the launch call,
-            # which put the host launch gap inside the pair: 20.7 us where the trace says 14.8 us). = 2 (BENCH_PROFILE_MODE=2) captures
-            # record-event nodes into the hipGraphs, but on ROCm 7.2 those cannot be read back (hipEventElapsedTime fails): falls back to 1.
-            pmode = int(os.environ.get("BENCH_PROFILE_MODE", "1"))
-            be.set_option("profile", pmode); m.kv_clear(); run_tokens(min(K, 32)); prof = be.profile()
-            if not prof and pmode == 2:
-                be.set_option("profile", 1); m.kv_clear(); run_tokens(min(K, 32)); prof = be.profile()
-            be.set_option("profile", 0)
-            roof, top = roofline_from_profile(prof)
-            # HBM bytes per launch of that kernel from the PMC pass (a separate rocprofv3 --pmc FETCH_SIZE run, doubled as the guide's
-            # gfx950 correction prescribes; tools/pmc_traffic.py) — it cannot be collected inside this run, so the committed summary
-            # of the same workload is quoted (the newest round's), and only when its kernel is the dominant launch found live
-            try:
-                pdir = os.path.join(os.path.dirname(os.path.abspath(__file__)), "profiles")
-                for fn in ("r04_pmc_fetch_size_summary.json", "r03_pmc_fetch_size_summary.json", "r02_pmc_fetch_size_summary.json", "r01_l_pmc_fetch_size_summary.json"):
-                    pmc_file = os.path.join(pdir, fn)
-                    if roof["traffic"] is not None or not (args.model == "llama3-8b" and args.ftype == "Q4_K_M" and os.path.exists(pmc_file)):
-                        continue
-                    for e in json.load(open(pmc_file)):
-                        t = e.get("hbm_read_bytes_per_launch_corrected")
-                        same = (top.get("kernel") or "k_mmvq_fused") in e["kernel"]
-                        if same and t and abs(t - top["bytes_per_launch"]) <= 0.05 * top["bytes_per_launch"]:
-                            roof["traffic"] = int(t)
-                            roof["traffic_source"] = f"profiles/{fn} ({e['kernel']}): a separate rocprofv3 --pmc FETCH_SIZE pass of this workload, x2 per the gfx950 correction; not collected in this run"
-                            break
-            except Exception:
-                pass
-        # achievable streaming-read rate on this box, same load instruction as the kernels
-        import ctypes as C
-        p = gg.base().ggml_backend_reg_get_proc_address(be.reg, b"ggml_backend_mi355x_test_hbm_read_gbps")
-        hbm = C.CFUNCTYPE(C.c_double, C.c_void_p, C.c_size_t, C.c_int)(p)
-        extra["hbm_read_probe_GBps"] = round(max(hbm(be.be, 2 << 30, 5) for _ in range(2)), 1)
-        m.free()
-
-        if args.pp > 0:
-            mp = new_model(args.pp, flash_attn=bool(args.fa))
-            ptoks = rng.integers(0, cfg["n_vocab"], size=args.pp).astype(np.int32)
-            mp.decode(ptoks); mp.kv_clear()                       # warm-up prompt pass (llama-bench.cpp:1949-1971)
-            reps = []
-            for _ in range(3):
-                mp.kv_clear(); torch.cuda.synchronize(); t0 = time.perf_counter(); mp.decode(ptoks); torch.cuda.synchronize()
-                reps.append(args.pp / (time.perf_counter() - t0))
-            extra[f"pp{args.pp}_tok_s"] = round(float(np.mean(reps)), 1)
-            # the prompt pass against the matrix cores: 2 FLOP per token and weight element of the layers' mat-muls (MoE: the used experts), the attention
-            # products on top; dense bf16 MFMA peak from MI355X_MICROARCH.md (2.5 PFLOP/s)
-            hd, nh, nkv, ne, nff = cfg["n_embd_head"], cfg["n_head"], cfg["n_head_kv"], cfg["n_embd"], cfg["n_ff"]
-            w_layer = ne*(nh*hd + 2*nkv*hd) + nh*hd*ne + 3*ne*nff*max(1, cfg.get("n_expert_used", 0))
-            flop = 2.0*args.pp*w_layer*cfg["n_layer"] + 2.0*2.0*nh*hd*cfg["n_layer"]*args.pp*(args.pp + 1)/2
-            tfs = flop*float(np.mean(reps))/args.pp/1e12
-            extra[f"pp{args.pp}_mfma"] = {"TFLOP_per_pass": round(flop/1e12, 3), "achieved_TFLOPs": round(tfs, 1), "peak_TFLOPs": 2500.0, "frac": round(tfs/2500.0, 4)}
-            mp.free()
-        result["extra"] = extra
-        result["roofline"] = roof
-        if args.parity:
-            try:
-                extra["perplexity"] = perplexity_delta(be, ls, gg, args.ftype, gguf=args.gguf, positions=args.parity_positions)
-            except Exception as e:
-                extra["perplexity"] = {"failed": str(e)}
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, {"logits": logits})
+        if not args.full:
+            m.free()
         else:
-            extra["parity_skipped"] = True      # (--parity runs the checker leg; the GPU test suite holds its gates)
-        if not args.no_cpu_baseline:
-            try:
-                result["cpu_baseline"] = cpu_baseline(cfg, args.ftype)
-            except Exception as e:   # the baseline is reporting only; never let it take the bench line down
-                result["cpu_baseline"] = {"value": None, "unit": "tok/s", "cores": 0, "kind": "port", "sample": f"failed: {e}"}
+            cnt = be.counters()
+            extra = {"graph_replays": cnt["graph_replays"], "kernels_per_token": None, "graph_nodes": m.graph_nodes(1),
+                     "weight_GB_per_token": m.weight_bytes / 1e9,
+                     "hbm_frac_whole_token": (m.weight_bytes * tok_s / 1e9) / HBM_PEAK_GBPS}
+            # kernel count per token from one eager token
+            be.set_option("graphs", 0); m.kv_clear(); be.reset_counters(); run_tokens(1)
+            extra["kernels_per_token"] = be.counters()["kernels_launched"]
+            be.set_option("graphs", 1)
+
+            roof = None
+            if not args.no_profile and args.row_split <= 1:      # (the per-device launches of a row split are not bracketed: that mode reports throughput only)
+                # dominant kernel, timed live with HIP events on the backend stream. Option "profile" = 1: eager launches, each grouped mat-vec
+                # dispatch carrying its own start/stop event pair (hipExtLaunchKernelGGL), i.e. kernel start -> kernel end by the packet's
+                # timestamps, the same interval rocprofv3's kernel trace reports (round 1 recorded an event either side of the launch call,
+                # which put the host launch gap inside the pair: 20.7 us where the trace says 14.8 us). = 2 (BENCH_PROFILE_MODE=2) captures
+                # record-event nodes into the hipGraphs, but on ROCm 7.2 those cannot be read back (hipEventElapsedTime fails): falls back to 1.
+                pmode = int(os.environ.get("BENCH_PROFILE_MODE", "1"))
+                be.set_option("profile", pmode); m.kv_clear(); run_tokens(min(K, 32)); prof = be.profile()
+                if not prof and pmode == 2:
+                    be.set_option("profile", 1); m.kv_clear(); run_tokens(min(K, 32)); prof = be.profile()
+                be.set_option("profile", 0)
+                roof, top = roofline_from_profile(prof)
+                # HBM bytes per launch of that kernel from the PMC pass (a separate rocprofv3 --pmc FETCH_SIZE run, doubled as the guide's
+                # gfx950 correction prescribes; tools/pmc_traffic.py) — it cannot be collected inside this run, so the committed summary
+                # of the same workload is quoted (the newest round's), and only when its kernel is the dominant launch found live
+                try:
+                    pdir = os.path.join(os.path.dirname(os.path.abspath(__file__)), "profiles")
+                    for fn in ("r04_pmc_fetch_size_summary.json", "r03_pmc_fetch_size_summary.json", "r02_pmc_fetch_size_summary.json", "r01_l_pmc_fetch_size_summary.json"):
+                        pmc_file = os.path.join(pdir, fn)
+                        if roof["traffic"] is not None or not (args.model == "llama3-8b" and args.ftype == "Q4_K_M" and os.path.exists(pmc_file)):
+                            continue
+                        for e in json.load(open(pmc_file)):
+                            t = e.get("hbm_read_bytes_per_launch_corrected")
+                            same = (top.get("kernel") or "k_mmvq_fused") in e["kernel"]
+                            if same and t and abs(t - top["bytes_per_launch"]) <= 0.05 * top["bytes_per_launch"]:
+                                roof["traffic"] = int(t)
+                                roof["traffic_source"] = f"profiles/{fn} ({e['kernel']}): a separate rocprofv3 --pmc FETCH_SIZE pass of this workload, x2 per the gfx950 correction; not collected in this run"
+                                break
+                except Exception:
+                    pass
+            # achievable streaming-read rate on this box, same load instruction as the kernels
+            import ctypes as C
+            p = gg.base().ggml_backend_reg_get_proc_address(be.reg, b"ggml_backend_mi355x_test_hbm_read_gbps")
+            hbm = C.CFUNCTYPE(C.c_double, C.c_void_p, C.c_size_t, C.c_int)(p)
+            extra["hbm_read_probe_GBps"] = round(max(hbm(be.be, 2 << 30, 5) for _ in range(2)), 1)
+            m.free()
+
+            if args.pp > 0:
+                mp = new_model(args.pp, flash_attn=bool(args.fa))
+                ptoks = rng.integers(0, cfg["n_vocab"], size=args.pp).astype(np.int32)
+                mp.decode(ptoks); mp.kv_clear()                       # warm-up prompt pass (llama-bench.cpp:1949-1971)
+                reps = []
+                for _ in range(3):
+                    mp.kv_clear(); torch.cuda.synchronize(); t0 = time.perf_counter(); mp.decode(ptoks); torch.cuda.synchronize()
+                    reps.append(args.pp / (time.perf_counter() - t0))
+                extra[f"pp{args.pp}_tok_s"] = round(float(np.mean(reps)), 1)
+                # the prompt pass against the matrix cores: 2 FLOP per token and weight element of the layers' mat-muls (MoE: the used experts), the attention
+                # products on top; dense bf16 MFMA peak from MI355X_MICROARCH.md (2.5 PFLOP/s)
+                hd, nh, nkv, ne, nff = cfg["n_embd_head"], cfg["n_head"], cfg["n_head_kv"], cfg["n_embd"], cfg["n_ff"]
+                w_layer = ne*(nh*hd + 2*nkv*hd) + nh*hd*ne + 3*ne*nff*max(1, cfg.get("n_expert_used", 0))
+                flop = 2.0*args.pp*w_layer*cfg["n_layer"] + 2.0*2.0*nh*hd*cfg["n_layer"]*args.pp*(args.pp + 1)/2
+                tfs = flop*float(np.mean(reps))/args.pp/1e12
+                extra[f"pp{args.pp}_mfma"] = {"TFLOP_per_pass": round(flop/1e12, 3), "achieved_TFLOPs": round(tfs, 1), "peak_TFLOPs": 2500.0, "frac": round(tfs/2500.0, 4)}
+                mp.free()
+            result["extra"] = extra
+            result["roofline"] = roof
+            if args.parity:
+                try:
+                    extra["perplexity"] = perplexity_delta(be, ls, gg, args.ftype, gguf=args.gguf, positions=args.parity_positions)
+                except Exception as e:
+                    extra["perplexity"] = {"failed": str(e)}
+            else:
+                extra["parity_skipped"] = True      # (--parity runs the checker leg; the GPU test suite holds its gates)
+            if not args.no_cpu_baseline:
+                try:
+                    result["cpu_baseline"] = cpu_baseline(cfg, args.ftype)
+                except Exception as e:   # the baseline is reporting only; never let it take the bench line down
+                    result["cpu_baseline"] = {"value": None, "unit": "tok/s", "cores": 0, "kind": "port", "sample": f"failed: {e}"}
     else:
         n_embd = cfg["n_embd"]
         buf_dev = "cuda" if transport == "nccl" else "cpu"
@@ -365,6 +393,7 @@ def main():
         # per-stage clock (rank 0 prints every rank's numbers): seconds this rank spent computing its layers, blocked on the hand-off from the stage before,
         # and blocked on a send buffer still in flight — summed over the timed steps only
         clock = {"on": False, "compute": 0.0, "recv_wait": 0.0, "send_wait": 0.0}
+        last = {"logits": None}      # --dump-outputs: what the last rank's last timed step returned
 
         def post_recv(j):
             recv_work[j % lsp.N_BUF] = dist.irecv(recv_buf[j % lsp.N_BUF], src=rank - 1, group=pg)
@@ -401,6 +430,8 @@ def main():
                 clock["send_wait"] += t_c - t_in; clock["compute"] += time.perf_counter() - t_c
             if dump is not None and has_out and dump["on"]:
                 dump["rows"].append((seq, pos[seq], out.copy()))
+            if has_out and clock["on"]:
+                last["logits"] = out
             pos[seq] += 1
         log(f"[rank {rank}] warm-up: {W} pipeline steps")
         lsp.run_steps(tr, W, stage, 0, n_seq)
@@ -419,75 +450,77 @@ def main():
         clock["on"] = False
         log(f"[rank {rank}] timed steps done")
         sync_all(); dt = time.perf_counter() - t0
+        if dump is not None:
+            dump["on"] = False
         tmax = torch.tensor([dt], dtype=torch.float64)          # default group = gloo
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = float(tmax.item())
         result.update(value=K / dt, ms_per_step=dt / K * 1e3)
+        if args.dump_outputs and has_out:
+            dump_outputs(args.dump_outputs, {"logits": last["logits"]})
         result["extra"] = {"layers": [list(r) for r in ranges], "sequences_in_flight": n_seq, "handoff_bytes": n_embd * 4}
-        # hand-off latency, measured after the timed region: 32 ping-pongs of one hand-off message over every link in turn (rank r <-> r + 1), one way = half
-        # the round trip, through the same transport and buffers the pipeline uses
-        lat = [0.0] * world
-        for link in range(world - 1):
-            dist.barrier()
-            if rank in (link, link + 1):
-                peer = link + 1 if rank == link else link
-                for it in range(40):
-                    if it == 8: tcur.synchronize(); tl = time.perf_counter()
-                    if rank == link:
-                        dist.send(send_buf[0], dst=peer, group=pg); dist.recv(recv_buf[0], src=peer, group=pg)
-                    else:
-                        dist.recv(recv_buf[0], src=peer, group=pg); dist.send(send_buf[0], dst=peer, group=pg)
-                    tcur.synchronize()
-                if rank == link: lat[link] = (time.perf_counter() - tl) / 32 / 2 * 1e6
-        per_rank = torch.tensor([[clock["compute"], clock["recv_wait"], clock["send_wait"]] + lat], dtype=torch.float64)
-        gathered = [torch.zeros_like(per_rank) for _ in range(world)]
-        dist.all_gather(gathered, per_rank)                     # default group = gloo
-        result["extra"]["stages"] = [{"rank": r, "layers": list(ranges[r][:2]), "output_layer": bool(ranges[r][2]),
-                                      "compute_ms_per_step": round(float(gathered[r][0, 0]) / K * 1e3, 4),
-                                      "recv_wait_ms_per_step": round(float(gathered[r][0, 1]) / K * 1e3, 4),
-                                      "send_buffer_wait_ms_per_step": round(float(gathered[r][0, 2]) / K * 1e3, 4),
-                                      "handoff_to_next_one_way_us": round(float(gathered[r][0, 3 + r]), 1) if r < world - 1 else None} for r in range(world)]
-        result["extra"]["stages_note"] = ("host clocks around the synchronised stage call and around the blocking waits, timed steps only; a step's wall time = compute + "
-                                          "recv_wait + send_buffer_wait + loop overhead; the hand-off latency is a ping-pong of one n_embd x f32 message after the timed region")
-        # llama-bench's own -sm layer number: ONE sequence, a token does not start before the previous one is through the last stage
-        # (tools/llama-bench/llama-bench.cpp:1791-1810). Untimed by the contract's `value` (whole-job aggregate); reported beside it.
-        if dump is not None:
-            dump["on"] = False
-        ack = torch.zeros(1, dtype=torch.float32, device=buf_dev)
-        def token_done(j):
-            if rank == world - 1:
-                dist.send(ack, dst=0, group=pg)
-            elif rank == 0:
-                dist.recv(ack, src=world - 1, group=pg)
-            tcur.synchronize()
-        m.kv_clear()
-        for i in range(n_seq):
-            pos[i] = 0
-        kc = min(K, n_ctx - 1)
-        lsp.run_chain_steps(tr, min(8, kc), stage, token_done)      # warm-up of the one-sequence graphs
-        m.kv_clear(); pos[0] = 0
-        sync_all(); t0 = time.perf_counter()
-        lsp.run_chain_steps(tr, kc, stage, token_done)
-        sync_all(); dtc = time.perf_counter() - t0
-        tmax = torch.tensor([dtc], dtype=torch.float64)
-        dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
-        result["extra"]["single_sequence_chain_tok_s"] = round(kc / float(tmax.item()), 2)
-        result["extra"]["single_sequence_chain_note"] = "llama-bench's -sm layer protocol: one sequence, per-token synchronisation through all stages; does not scale with the GPU count by construction"
-        # the dominant kernel's roofline, from rank 0's own stage (the same kernel on every rank: each streams its layers' weights from its own HBM)
-        result["roofline"] = None
-        if rank == 0 and not args.no_profile:
-            try:
-                be.set_option("profile", 1); m.kv_clear(); pos[0] = 0
-                for j in range(min(kc, 16)):
-                    stage(0, j, False)
-                flush()
-                prof = be.profile(); be.set_option("profile", 0)
-                if prof:
-                    roof, _ = roofline_from_profile(prof)
-                    roof["note"] = "rank 0's stage only, timed after the throughput measurement"
-                    result["roofline"] = roof
-            except Exception as e:   # noqa: BLE001 — reporting only
-                log(f"[rank 0] roofline leg failed: {e}")
+        if args.full:
+            # hand-off latency, measured after the timed region: 32 ping-pongs of one hand-off message over every link in turn (rank r <-> r + 1), one way = half
+            # the round trip, through the same transport and buffers the pipeline uses
+            lat = [0.0] * world
+            for link in range(world - 1):
+                dist.barrier()
+                if rank in (link, link + 1):
+                    peer = link + 1 if rank == link else link
+                    for it in range(40):
+                        if it == 8: tcur.synchronize(); tl = time.perf_counter()
+                        if rank == link:
+                            dist.send(send_buf[0], dst=peer, group=pg); dist.recv(recv_buf[0], src=peer, group=pg)
+                        else:
+                            dist.recv(recv_buf[0], src=peer, group=pg); dist.send(send_buf[0], dst=peer, group=pg)
+                        tcur.synchronize()
+                    if rank == link: lat[link] = (time.perf_counter() - tl) / 32 / 2 * 1e6
+            per_rank = torch.tensor([[clock["compute"], clock["recv_wait"], clock["send_wait"]] + lat], dtype=torch.float64)
+            gathered = [torch.zeros_like(per_rank) for _ in range(world)]
+            dist.all_gather(gathered, per_rank)                     # default group = gloo
+            result["extra"]["stages"] = [{"rank": r, "layers": list(ranges[r][:2]), "output_layer": bool(ranges[r][2]),
+                                          "compute_ms_per_step": round(float(gathered[r][0, 0]) / K * 1e3, 4),
+                                          "recv_wait_ms_per_step": round(float(gathered[r][0, 1]) / K * 1e3, 4),
+                                          "send_buffer_wait_ms_per_step": round(float(gathered[r][0, 2]) / K * 1e3, 4),
+                                          "handoff_to_next_one_way_us": round(float(gathered[r][0, 3 + r]), 1) if r < world - 1 else None} for r in range(world)]
+            result["extra"]["stages_note"] = ("host clocks around the synchronised stage call and around the blocking waits, timed steps only; a step's wall time = compute + "
+                                              "recv_wait + send_buffer_wait + loop overhead; the hand-off latency is a ping-pong of one n_embd x f32 message after the timed region")
+            # llama-bench's own -sm layer number: ONE sequence, a token does not start before the previous one is through the last stage
+            # (tools/llama-bench/llama-bench.cpp:1791-1810). Untimed by the contract's `value` (whole-job aggregate); reported beside it.
+            ack = torch.zeros(1, dtype=torch.float32, device=buf_dev)
+            def token_done(j):
+                if rank == world - 1:
+                    dist.send(ack, dst=0, group=pg)
+                elif rank == 0:
+                    dist.recv(ack, src=world - 1, group=pg)
+                tcur.synchronize()
+            m.kv_clear()
+            for i in range(n_seq):
+                pos[i] = 0
+            kc = min(K, n_ctx - 1)
+            lsp.run_chain_steps(tr, min(8, kc), stage, token_done)      # warm-up of the one-sequence graphs
+            m.kv_clear(); pos[0] = 0
+            sync_all(); t0 = time.perf_counter()
+            lsp.run_chain_steps(tr, kc, stage, token_done)
+            sync_all(); dtc = time.perf_counter() - t0
+            tmax = torch.tensor([dtc], dtype=torch.float64)
+            dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
+            result["extra"]["single_sequence_chain_tok_s"] = round(kc / float(tmax.item()), 2)
+            result["extra"]["single_sequence_chain_note"] = "llama-bench's -sm layer protocol: one sequence, per-token synchronisation through all stages; does not scale with the GPU count by construction"
+            # the dominant kernel's roofline, from rank 0's own stage (the same kernel on every rank: each streams its layers' weights from its own HBM)
+            if rank == 0 and not args.no_profile:
+                try:
+                    be.set_option("profile", 1); m.kv_clear(); pos[0] = 0
+                    for j in range(min(kc, 16)):
+                        stage(0, j, False)
+                    flush()
+                    prof = be.profile(); be.set_option("profile", 0)
+                    if prof:
+                        roof, _ = roofline_from_profile(prof)
+                        roof["note"] = "rank 0's stage only, timed after the throughput measurement"
+                        result["roofline"] = roof
+                except Exception as e:   # noqa: BLE001 — reporting only
+                    log(f"[rank 0] roofline leg failed: {e}")
         dist.barrier()
         if dump is not None and has_out:
             np.savez(os.environ["BENCH_DUMP_LOGITS"], seq=np.array([r[0] for r in dump["rows"]]), pos=np.array([r[1] for r in dump["rows"]]),

@@ -145,7 +145,7 @@ def test_bench_runs_on_a_gguf_file(golden_dir):
     import sys
     from pathlib import Path
     root = Path(__file__).resolve().parent.parent
-    r = subprocess.run([sys.executable, str(root / "bench.py"), "--gguf", str(golden_dir / NAME), "--steps", "16", "--warmup", "4", "--pp", "32", "--no-cpu-baseline"],
+    r = subprocess.run([sys.executable, str(root / "bench.py"), "--gguf", str(golden_dir / NAME), "--steps", "16", "--warmup", "4", "--full", "--pp", "32", "--no-cpu-baseline"],
                        capture_output=True, text=True, timeout=600, env=dict(os.environ))
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

@@ -33,7 +33,7 @@ def test_two_rank_layer_split_equals_single_process(ftype, tmp_path):
     env = dict(os.environ, BENCH_TRANSPORT="gloo", BENCH_DUMP_LOGITS=str(dump), MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={G}", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), str(ROOT / "bench.py"), "--gpus", str(G), "--steps", str(K), "--warmup", str(W),
-           "--model", "tiny4", "--ftype", ftype, "--no-cpu-baseline", "--no-profile", "--pp", "0"]
+           "--model", "tiny4", "--ftype", ftype, "--full", "--no-cpu-baseline", "--no-profile", "--pp", "0"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=str(ROOT))
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
