@@ -73,6 +73,9 @@ struct ggml_backend_mi355x_counters {
     uint64_t act_quant_launches;
     uint64_t act_quant_reused;     // MUL_MATs that reused the previous node's quantized activations
     uint64_t split_mul_mats;       // MUL_MATs on row-split weights (one launch per device that holds rows)
+    uint64_t graph_partial_replays;  // graph_compute calls that launched a cached graph's leading segments and then the rest: eagerly, or from the
+                                     // segments of this graph's own entry (captured then, or earlier) that begin where the matched prefix ends
+    uint64_t moe_combine_direct;     // MoE combines that took their routing weights from the fused router's hand-off (moe_ws) instead of the probabilities
 };
 // Row-split weights (-sm row). Replaces ggml_backend_cuda_split_buffer_type, which the host finds through the registry proc
 // "ggml_backend_split_buffer_type" (src/llama-model.cpp:368-387; typedef ggml_backend_split_buffer_type_t, ggml-backend.h): main_device is

@@ -388,8 +388,10 @@ struct mi_backend_ctx {
     int moe_dual = -1;                  // option "moe_dual"
     float * moe_ws = nullptr;                                   // logits + arrival counter of the multi-workgroup router kernel (moe_route)
     // the last router launch of this graph pass: it ranked `vals` (probabilities, or logits) into `sorted` and left the eight best values in rank order at moe_ws + 64
-    // (floats the kernel does not use otherwise): a combine that gathers vals[sorted[u]] takes them from there — one load instead of two dependent cold ones
-    struct { bool valid = false; const void * vals = nullptr; const void * sorted = nullptr; } rt;
+    // (floats the kernel does not use otherwise): a combine that gathers vals[sorted[u]] takes them from there — one load instead of two dependent cold ones.
+    // Keyed on addresses, so any later node that writes over vals or sorted (an allocator reuses a dead router's memory for the next layer's, whose router
+    // may run unfused) ends it; nodes lo..hi are the router launch's own.
+    struct { bool valid = false; const void * vals = nullptr; const void * sorted = nullptr; size_t bytes = 0; int lo = 0, hi = -1; } rt;
     // producer-side activation quantization (mmvq_fin): the image a GLU launch writes for the mat-vec that follows + its arrival counters
     void * fin_img = nullptr; unsigned * fin_cnt = nullptr;
     // the rotation table of the token being decoded ((cos, sin) per pair index; mmvq_rope::table): filled by one small launch when a graph's
@@ -779,21 +781,23 @@ static act_q8 get_act(mi_backend_ctx * c, const void * x, int64_t k, int64_t n_i
 
 static constexpr int ACT_KIND_BF16 = -16;   // aq.kind of the dense bf16 copy the MFMA prefill kernel reads
 
+// F16 activations of a quantized mat-mul (tests/test-backend-ops.cpp:5715-5716): a dense F32 copy in c->cvt first (the CPU backend converts src1 to the
+// weights' vec_dot type row by row as well), then the F32 path reads `tmp`, the copy's descriptor
+static const struct ggml_tensor * f16_src1_to_f32(mi_backend_ctx * c, const struct ggml_tensor * b, struct ggml_tensor & tmp) {
+    tmp = *b; tmp.type = GGML_TYPE_F32; tmp.data = c->cvt;
+    tmp.nb[0] = 4; tmp.nb[1] = (size_t) b->ne[0]*4; tmp.nb[2] = tmp.nb[1]*b->ne[1]; tmp.nb[3] = tmp.nb[2]*b->ne[2];
+    cpy(desc(b), desc(&tmp), c->stream);
+    c->cnt.kernels_launched++;
+    c->aq.valid = false;
+    return &tmp;
+}
+
 // out/res: the prefill residual fusion (try_fused_prefill_add) writes W.x + res into `out` instead of W.x into dst
 static void op_mul_mat(mi_backend_ctx * c, struct ggml_tensor * dst, struct ggml_tensor * out = nullptr, const struct ggml_tensor * res = nullptr, mmq_deferred * defer = nullptr) {
     const struct ggml_tensor * a = dst->src[0];
     const struct ggml_tensor * b = dst->src[1];
     struct ggml_tensor b32;
-    if (ggml_is_quantized(a->type) && b->type == GGML_TYPE_F16) {
-        // F16 activations (tests/test-backend-ops.cpp:5715-5716): a dense F32 copy first (the CPU backend converts src1 to the weights' vec_dot type row by row as well),
-        // then the F32 path
-        b32 = *b; b32.type = GGML_TYPE_F32; b32.data = c->cvt;
-        b32.nb[0] = 4; b32.nb[1] = (size_t) b->ne[0]*4; b32.nb[2] = b32.nb[1]*b->ne[1]; b32.nb[3] = b32.nb[2]*b->ne[2];
-        cpy(desc(b), desc(&b32), c->stream);
-        c->cnt.kernels_launched++;
-        c->aq.valid = false;
-        b = &b32;
-    }
+    if (ggml_is_quantized(a->type) && b->type == GGML_TYPE_F16) b = f16_src1_to_f32(c, b, b32);
     if (ggml_is_quantized(a->type)) {
         const int kind = act_kind_for((int) a->type);
         const int64_t K = a->ne[0], M = a->ne[1], N = b->ne[1];
@@ -862,6 +866,8 @@ static void op_mul_mat(mi_backend_ctx * c, struct ggml_tensor * dst, struct ggml
 static void op_mul_mat_split(mi_backend_ctx * c, struct ggml_tensor * dst) {
     const struct ggml_tensor * a = dst->src[0];
     const struct ggml_tensor * b = dst->src[1];
+    struct ggml_tensor b32;
+    if (b->type == GGML_TYPE_F16) b = f16_src1_to_f32(c, b, b32);      // (converted on the main device: the peers read it from there, as they read F32 activations)
     const mi_split_tensor * e = (const mi_split_tensor *) a->extra;
     const int kind = act_kind_for((int) a->type);
     const int64_t K = a->ne[0], N = b->ne[1];
@@ -1421,6 +1427,7 @@ static int try_fused_moe_combine(mi_backend_ctx * c, struct ggml_cgraph * g, int
     static const bool defer_on = !getenv("GGML_MI355X_MOE_COMBINE_DEFER") || atoi(getenv("GGML_MI355X_MOE_COMBINE_DEFER")) != 0;
     // the values this combine gathers are the ones the router just ranked (same tensors): its top-8 list is probs[ids[u]] already
     const bool direct = c->rt.valid && c->moe_ws && pr->data == c->rt.vals && ids->data == c->rt.sorted && ids->nb[0] == 4;
+    if (direct) c->cnt.moe_combine_direct++;
     {
         const int jn = next_real(g, jl);
         const int jm2 = jn > 0 ? next_real(g, jn) : -1;
@@ -1775,6 +1782,7 @@ static int try_fused_moe_route(mi_backend_ctx * c, struct ggml_cgraph * g, int i
         moe_route((const float *) w->data, w->nb[1], (const float *) x->data, bias, K, E, softmax, logits_out, probs_out, (int32_t *) nd->data, c->stream, c->moe_ws, nullptr, 0.0f, nullptr, c->err_dev, topv);
     }
     c->rt.valid = topv != nullptr; c->rt.vals = softmax ? (const void *) probs_out : (const void *) logits_out; c->rt.sorted = nd->data;
+    c->rt.bytes = (size_t) E*4; c->rt.lo = i; c->rt.hi = j;
     c->cnt.kernels_launched++;
     return j - i + 1;
 }
@@ -2184,6 +2192,11 @@ done:
         if (c->aq.valid && !fresh_aq && w->data && ranges_overlap(w->data, ggml_nbytes(w), c->aq.data, c->aq.span)) {
             c->aq.valid = false;
         }
+        // ... and into what the last fused router ranked, unless it is that router's own node
+        if (c->rt.valid && (j < c->rt.lo || j > c->rt.hi) && w->data &&
+            (ranges_overlap(w->data, ggml_nbytes(w), c->rt.vals, c->rt.bytes) || ranges_overlap(w->data, ggml_nbytes(w), c->rt.sorted, c->rt.bytes))) {
+            c->rt.valid = false;
+        }
     }
     c->cnt.nodes_computed += consumed;
     return consumed;
@@ -2197,7 +2210,7 @@ done:
 // What makes launching a prefix safe: (1) a TOPOLOGY pass over the whole graph first (every node and its source tensors are the cached graph's: who reads
 // what decides which intermediates a fused group may leave unwritten); (2) a segment is launched only once its nodes' full signatures (op, type, shape,
 // strides, placement, op_params, the sources' placement and layout) match and every segment before it has been launched. If a later segment does not
-// match (same topology, another parameter), the remaining nodes run eagerly, behind the prefix already launched.
+// match (same topology, another parameter), the rest follows the prefix already launched (graph_compute_suffix).
 static void end_capture_segment(mi_backend_ctx * c, graph_entry & e, int begin, int end) {
     hipGraph_t graph = nullptr;
     MI_CHECK_G(hipStreamEndCapture(c->stream, &graph));
@@ -2344,6 +2357,104 @@ static graph_entry & graph_lookup(mi_backend_ctx * c, const struct ggml_cgraph *
     return e;
 }
 
+// the buffers a graph needs: allocated outside any capture (a captured graph holds their addresses). Growing one synchronizes the stream first (work
+// already queued, a replayed prefix included, may still read the old allocation) and drops every captured graph.
+static enum ggml_status prepare_buffers(mi_backend_ctx * c, const struct ggml_cgraph * g) {
+    if (!c->rope_tab) { if (hipMalloc((void **) &c->rope_tab, 4096) != hipSuccess) { (void) hipGetLastError(); c->rope_tab = nullptr; } }
+    if (!c->moe_ws) {
+        if (hipMalloc((void **) &c->moe_ws, 4096) == hipSuccess) { MI_CHECK_G(hipMemsetAsync(c->moe_ws, 0, 4096, c->stream)); MI_CHECK_G(hipStreamSynchronize(c->stream)); }
+        else { (void) hipGetLastError(); c->moe_ws = nullptr; }
+    }
+    if (!c->err_host) {      // the error words of the kernels with bounded waits (host-mapped)
+        if (hipHostMalloc((void **) &c->err_host, 64, hipHostMallocMapped) == hipSuccess && hipHostGetDevicePointer((void **) &c->err_dev, c->err_host, 0) == hipSuccess) memset(c->err_host, 0, 64);
+        else { (void) hipGetLastError(); c->err_host = nullptr; c->err_dev = nullptr; }
+    }
+    if (!c->fin_img) {       // allocated once, outside any capture; the counters are zero between launches (the kernels re-arm them)
+        if (hipMalloc(&c->fin_img, mi_backend_ctx::FIN_IMG_BYTES) != hipSuccess) { (void) hipGetLastError(); c->fin_img = nullptr; }
+        if (c->fin_img && hipMalloc((void **) &c->fin_cnt, (mi_backend_ctx::FIN_COUNTERS + 8)*4) == hipSuccess) {
+            MI_CHECK_G(hipMemsetAsync(c->fin_cnt, 0, (mi_backend_ctx::FIN_COUNTERS + 8)*4, c->stream)); MI_CHECK_G(hipStreamSynchronize(c->stream));
+        } else if (c->fin_img) { (void) hipGetLastError(); (void) hipFree(c->fin_img); c->fin_img = nullptr; c->fin_cnt = nullptr; }
+    }
+    if (!c->attn_part) {     // <= 8 tokens x 128 heads x 32 ranges x (128 + 2) floats: allocated once, outside any capture
+        const size_t pb = (size_t) 8*128*32*130*4;
+        if (hipMalloc((void **) &c->attn_part, pb) == hipSuccess) c->attn_part_bytes = pb; else (void) hipGetLastError();
+    }
+    const size_t need = graph_scratch_need(g);
+    if (need > c->scratch_size) {
+        MI_CHECK_G(hipStreamSynchronize(c->stream));
+        if (c->scratch) MI_CHECK_G(hipFree(c->scratch));
+        c->scratch = nullptr; c->scratch_size = 0;
+        drop_graphs(c);   // captured graphs hold the old scratch pointer
+        const size_t sz = need + (need >> 2);
+        if (hipMalloc(&c->scratch, sz) != hipSuccess) { (void) hipGetLastError(); return GGML_STATUS_ALLOC_FAILED; }
+        c->scratch_size = sz;
+    }
+    {
+        size_t kv_need = 0;
+        for (int i = 0; i < g->n_nodes; i++) if (g->nodes[i]->op == GGML_OP_FLASH_ATTN_EXT) { size_t kb, vb; fa_kv16_plan(g->nodes[i], kb, vb); kv_need = std::max(kv_need, kb + vb); }
+        if (kv_need > c->kv16_size) {
+            MI_CHECK_G(hipStreamSynchronize(c->stream));
+            if (c->kv16) MI_CHECK_G(hipFree(c->kv16));
+            c->kv16 = nullptr; c->kv16_size = 0;
+            drop_graphs(c);   // captured graphs hold the old pointer
+            const size_t sz = kv_need + (kv_need >> 1);      // (the cache view grows with the context: fewer re-allocations)
+            if (hipMalloc(&c->kv16, sz) != hipSuccess) { (void) hipGetLastError(); return GGML_STATUS_ALLOC_FAILED; }
+            c->kv16_size = sz;
+        }
+    }
+
+    {
+        size_t cv_need = 0;
+        for (int i = 0; i < g->n_nodes; i++) {
+            const struct ggml_tensor * nd = g->nodes[i];
+            if (nd->op == GGML_OP_MUL_MAT && ggml_is_quantized(nd->src[0]->type) && nd->src[1]->type == GGML_TYPE_F16) cv_need = std::max(cv_need, (size_t) ggml_nelements(nd->src[1])*4 + 256);
+        }
+        if (cv_need > c->cvt_size) {
+            MI_CHECK_G(hipStreamSynchronize(c->stream));
+            if (c->cvt) MI_CHECK_G(hipFree(c->cvt));
+            c->cvt = nullptr; c->cvt_size = 0;
+            drop_graphs(c);
+            if (hipMalloc(&c->cvt, cv_need) != hipSuccess) { (void) hipGetLastError(); return GGML_STATUS_ALLOC_FAILED; }
+            c->cvt_size = cv_need;
+        }
+    }
+
+    return GGML_STATUS_SUCCESS;
+}
+
+// ---- replay, partial match: a cached graph's segments before node `resume` are on the stream; this graph differs from it behind them ----
+// (llama.cpp rebuilds a graph in the same memory when n_kv moves to the next bucket: same nodes, the attention's shapes changed). The rest still needs
+// buffers sized for THIS graph, before any of its nodes runs (a larger K / V conversion, more scratch), and its signature counts like any other: on
+// its second sighting the whole graph is captured — recording runs nothing — and only the segments behind the prefix are launched; from then on the
+// fast path replays it in full. Growing a buffer behind the prefix loses nothing the suffix reads: what prepare_buffers may replace (scratch, kv16,
+// cvt) holds nothing across a cut — the cached activations are dropped at every cut and the deferred combine never spans one — and what does cross a
+// cut (the rotation table, the router's top values at moe_ws + 64, the producer images in fin_img, attn_part) lives in buffers allocated once and never
+// replaced; the prefix launched is the one this graph's own capture would hold, so it leaves the same values there.
+static enum ggml_status graph_compute_suffix(mi_backend_ctx * c, struct ggml_cgraph * g, int resume) {
+    const enum ggml_status st = prepare_buffers(c, g);
+    if (st != GGML_STATUS_SUCCESS) return st;
+    graph_entry & e = graph_lookup(c, g);
+    if (e.segs.empty() && e.seen >= 2) {
+        c->cap_entry = &e;
+        MI_CHECK_G(hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
+        c->prof_suspend = false;
+        c->capturing = true;
+        run_nodes(c, g, 0, &e);
+        c->cap_entry = nullptr;
+        c->prof_suspend = c->prof_in_graph;
+        c->cnt.graph_captures++;
+    }
+    size_t si = 0;
+    while (si < e.segs.size() && e.segs[si].begin < resume) si++;
+    if (si < e.segs.size() && e.segs[si].begin == resume) {
+        for (; si < e.segs.size(); si++) if (e.segs[si].exec) MI_CHECK_G(hipGraphLaunch(e.segs[si].exec, c->stream));
+        return GGML_STATUS_SUCCESS;
+    }
+    c->prof_suspend = false;
+    run_nodes(c, g, resume);
+    return GGML_STATUS_SUCCESS;
+}
+
 static enum ggml_status be_graph_compute_impl(ggml_backend_t backend, struct ggml_cgraph * g);
 static double g_host_ns = 0.0; static long g_host_calls = 0;     // GGML_MI355X_HOST_TIMING=1: host time spent inside graph_compute
 static enum ggml_status be_graph_compute(ggml_backend_t backend, struct ggml_cgraph * g) {
@@ -2413,72 +2524,16 @@ static enum ggml_status be_graph_compute_impl(ggml_backend_t backend, struct ggm
                 }
                 return GGML_STATUS_SUCCESS;
             }
-            if (si > 0) {      // same topology, a parameter changed behind an identical prefix: the prefix is on the stream, the rest runs eagerly
-                c->prof_suspend = false;
-                run_nodes(c, g, e->segs[si].begin);
-                return GGML_STATUS_SUCCESS;
+            if (si > 0) {      // same topology, a parameter changed behind an identical prefix: the prefix is on the stream, the rest follows it
+                c->cnt.graph_partial_replays++;
+                return graph_compute_suffix(c, g, e->segs[si].begin);
             }
         }
     }
 
-    // ---- everything else: buffers this graph needs (allocated outside any capture; a captured graph holds their addresses) ----
-    if (!c->rope_tab) { if (hipMalloc((void **) &c->rope_tab, 4096) != hipSuccess) { (void) hipGetLastError(); c->rope_tab = nullptr; } }
-    if (!c->moe_ws) {
-        if (hipMalloc((void **) &c->moe_ws, 4096) == hipSuccess) { MI_CHECK_G(hipMemsetAsync(c->moe_ws, 0, 4096, c->stream)); MI_CHECK_G(hipStreamSynchronize(c->stream)); }
-        else { (void) hipGetLastError(); c->moe_ws = nullptr; }
-    }
-    if (!c->err_host) {      // the error words of the kernels with bounded waits (host-mapped)
-        if (hipHostMalloc((void **) &c->err_host, 64, hipHostMallocMapped) == hipSuccess && hipHostGetDevicePointer((void **) &c->err_dev, c->err_host, 0) == hipSuccess) memset(c->err_host, 0, 64);
-        else { (void) hipGetLastError(); c->err_host = nullptr; c->err_dev = nullptr; }
-    }
-    if (!c->fin_img) {       // allocated once, outside any capture; the counters are zero between launches (the kernels re-arm them)
-        if (hipMalloc(&c->fin_img, mi_backend_ctx::FIN_IMG_BYTES) != hipSuccess) { (void) hipGetLastError(); c->fin_img = nullptr; }
-        if (c->fin_img && hipMalloc((void **) &c->fin_cnt, (mi_backend_ctx::FIN_COUNTERS + 8)*4) == hipSuccess) {
-            MI_CHECK_G(hipMemsetAsync(c->fin_cnt, 0, (mi_backend_ctx::FIN_COUNTERS + 8)*4, c->stream)); MI_CHECK_G(hipStreamSynchronize(c->stream));
-        } else if (c->fin_img) { (void) hipGetLastError(); (void) hipFree(c->fin_img); c->fin_img = nullptr; c->fin_cnt = nullptr; }
-    }
-    if (!c->attn_part) {     // <= 8 tokens x 128 heads x 32 ranges x (128 + 2) floats: allocated once, outside any capture
-        const size_t pb = (size_t) 8*128*32*130*4;
-        if (hipMalloc((void **) &c->attn_part, pb) == hipSuccess) c->attn_part_bytes = pb; else (void) hipGetLastError();
-    }
-    const size_t need = graph_scratch_need(g);
-    if (need > c->scratch_size) {
-        MI_CHECK_G(hipStreamSynchronize(c->stream));
-        if (c->scratch) MI_CHECK_G(hipFree(c->scratch));
-        c->scratch = nullptr; c->scratch_size = 0;
-        drop_graphs(c);   // captured graphs hold the old scratch pointer
-        const size_t sz = need + (need >> 2);
-        if (hipMalloc(&c->scratch, sz) != hipSuccess) { (void) hipGetLastError(); return GGML_STATUS_ALLOC_FAILED; }
-        c->scratch_size = sz;
-    }
     {
-        size_t kv_need = 0;
-        for (int i = 0; i < g->n_nodes; i++) if (g->nodes[i]->op == GGML_OP_FLASH_ATTN_EXT) { size_t kb, vb; fa_kv16_plan(g->nodes[i], kb, vb); kv_need = std::max(kv_need, kb + vb); }
-        if (kv_need > c->kv16_size) {
-            MI_CHECK_G(hipStreamSynchronize(c->stream));
-            if (c->kv16) MI_CHECK_G(hipFree(c->kv16));
-            c->kv16 = nullptr; c->kv16_size = 0;
-            drop_graphs(c);   // captured graphs hold the old pointer
-            const size_t sz = kv_need + (kv_need >> 1);      // (the cache view grows with the context: fewer re-allocations)
-            if (hipMalloc(&c->kv16, sz) != hipSuccess) { (void) hipGetLastError(); return GGML_STATUS_ALLOC_FAILED; }
-            c->kv16_size = sz;
-        }
-    }
-
-    {
-        size_t cv_need = 0;
-        for (int i = 0; i < g->n_nodes; i++) {
-            const struct ggml_tensor * nd = g->nodes[i];
-            if (nd->op == GGML_OP_MUL_MAT && ggml_is_quantized(nd->src[0]->type) && nd->src[1]->type == GGML_TYPE_F16) cv_need = std::max(cv_need, (size_t) ggml_nelements(nd->src[1])*4 + 256);
-        }
-        if (cv_need > c->cvt_size) {
-            MI_CHECK_G(hipStreamSynchronize(c->stream));
-            if (c->cvt) MI_CHECK_G(hipFree(c->cvt));
-            c->cvt = nullptr; c->cvt_size = 0;
-            drop_graphs(c);
-            if (hipMalloc(&c->cvt, cv_need) != hipSuccess) { (void) hipGetLastError(); return GGML_STATUS_ALLOC_FAILED; }
-            c->cvt_size = cv_need;
-        }
+        const enum ggml_status st = prepare_buffers(c, g);
+        if (st != GGML_STATUS_SUCCESS) return st;
     }
 
     c->split_graph = false;

@@ -173,6 +173,9 @@ struct graph_inst {
     ggml_tensor * kq_mask_swa = nullptr, * k_idxs_swa = nullptr, * v_idxs_swa = nullptr;     // the window cache's own inputs (llm_graph_input_attn_kv_unified_iswa)
     ggml_tensor * result = nullptr;    // logits (has_output) or the last layer's l_out
     int64_t last_use = 0;
+    // the tensors whose extent is n_kv (or the window cache's n_kv): dimension `dim`; `contig` ones get their strides recomputed (MI_HARNESS_REUSE_GRAPH)
+    struct kv_dep { ggml_tensor * t; int dim; bool swa; bool contig; };
+    std::vector<kv_dep> kv_deps;
 };
 
 } // namespace
@@ -349,11 +352,14 @@ graph_inst build_graph(mi_llama * m, int seq, int n_tokens, int n_kv, int n_kv_s
     // with flash attention the mask is cast to F16 once per graph (src/llama-graph.cpp:1423)
     ggml_tensor * kq_mask_f16 = hp.flash_attn ? ggml_cast(ctx0, g.kq_mask, GGML_TYPE_F16) : nullptr;
     ggml_tensor * kq_mask_swa_f16 = nullptr;
+    auto kv_dep = [&](ggml_tensor * t, int dim, bool swa, bool contig) { if (t) g.kv_deps.push_back({ t, dim, swa, contig }); };
+    kv_dep(g.kq_mask, 0, false, true); kv_dep(kq_mask_f16, 0, false, true);
     if (m->swa_size > 0) {     // build_attn_inp_kv_unified_iswa (src/llama-graph.cpp:1568-1612): a second set of inputs for the window cache
         g.kq_mask_swa = ggml_new_tensor_2d(ctx0, GGML_TYPE_F32, n_kv_swa, GGML_PAD(n_tokens, GGML_KQ_MASK_PAD)); ggml_set_input(g.kq_mask_swa);
         g.k_idxs_swa  = ggml_new_tensor_1d(ctx0, GGML_TYPE_I64, n_tokens);                                         ggml_set_input(g.k_idxs_swa);
         g.v_idxs_swa  = ggml_new_tensor_1d(ctx0, GGML_TYPE_I64, hp.flash_attn ? n_tokens : n_tokens*n_embd_v_gqa); ggml_set_input(g.v_idxs_swa);
         if (hp.flash_attn) kq_mask_swa_f16 = ggml_cast(ctx0, g.kq_mask_swa, GGML_TYPE_F16);
+        kv_dep(g.kq_mask_swa, 0, true, true); kv_dep(kq_mask_swa_f16, 0, true, true);
     }
     const int n_outputs = 1;                                                       // llama_batch_get_one: logits for the last token only
     g.out_ids  = ggml_new_tensor_1d(ctx0, GGML_TYPE_I32, n_outputs);                ggml_set_input(g.out_ids);
@@ -427,11 +433,13 @@ graph_inst build_graph(mi_llama * m, int seq, int n_tokens, int n_kv, int n_kv_s
                 ggml_row_size(tv, hd), ggml_row_size(tv, n_embd_v_gqa), ggml_row_size(tv, n_embd_v_gqa*kv_size), 0)
             : ggml_view_4d(ctx0, L.v_cache[seq], n_kv_l, n_head_kv, hd, 1,
                 ggml_row_size(GGML_TYPE_F16, kv_size*hd), ggml_row_size(GGML_TYPE_F16, kv_size), ggml_row_size(GGML_TYPE_F16, kv_size*n_embd_v_gqa), 0);
+        kv_dep(k, 2, L.swa, false); kv_dep(v, hp.flash_attn ? 2 : 0, L.swa, false);
         if (hp.flash_attn) {   // build_attn_mha with flash attention (src/llama-graph.cpp:1245-1265, :1337): n_kv % 256 == 0 by the cache's padding
             ggml_tensor * q = ggml_reshape_4d(ctx0, Qcur, Qcur->ne[0], Qcur->ne[1], Qcur->ne[2], 1);
             q = ggml_permute(ctx0, q, 0, 2, 1, 3);
             k = ggml_permute(ctx0, k, 0, 2, 1, 3);
             v = ggml_permute(ctx0, v, 0, 2, 1, 3);
+            kv_dep(k, 1, L.swa, false); kv_dep(v, 1, L.swa, false);
             cur = ggml_flash_attn_ext(ctx0, q, k, v, l_mask_f16, kq_scale, 0.0f, 0.0f);
             ggml_flash_attn_ext_add_sinks(cur, L.sinks);
             ggml_flash_attn_ext_set_prec(cur, GGML_PREC_F32);
@@ -443,8 +451,10 @@ graph_inst build_graph(mi_llama * m, int seq, int n_tokens, int n_kv, int n_kv_s
             k = ggml_permute(ctx0, k, 0, 2, 1, 3);
             v = ggml_permute(ctx0, v, 0, 2, 1, 3);
             ggml_tensor * kq = ggml_mul_mat(ctx0, k, q);
+            kv_dep(k, 1, L.swa, false); kv_dep(v, 0, L.swa, false); kv_dep(kq, 0, L.swa, true);
             ggml_mul_mat_set_prec(kq, GGML_PREC_F32);
             kq = ggml_soft_max_ext(ctx0, kq, l_mask, kq_scale, 0.0f);
+            kv_dep(kq, 0, L.swa, true);
             if (L.sinks) ggml_soft_max_add_sinks(kq, L.sinks);       // build_attn_with_sinks, src/llama-graph.cpp:1313
             ggml_tensor * kqv = ggml_mul_mat(ctx0, v, kq);
             cur = ggml_permute(ctx0, kqv, 0, 2, 1, 3);
@@ -505,6 +515,15 @@ graph_inst build_graph(mi_llama * m, int seq, int n_tokens, int n_kv, int n_kv_s
         }
     }
     return g;
+}
+
+// MI_HARNESS_REUSE_GRAPH: the graph of a (seq, n_tokens) pair was built for the largest n_kv; this sets the extent of every tensor that depends on it
+// in place, as llama.cpp's rebuild in the same buf_compute_meta leaves the same node objects at the same addresses
+static void set_graph_n_kv(graph_inst & g, int n_kv, int n_kv_swa) {
+    for (const graph_inst::kv_dep & d : g.kv_deps) {
+        d.t->ne[d.dim] = d.swa ? n_kv_swa : n_kv;
+        if (d.contig) for (int i = 1; i < GGML_MAX_DIMS; i++) d.t->nb[i] = d.t->nb[i - 1]*d.t->ne[i - 1];
+    }
 }
 
 void free_graph(graph_inst & g) {
@@ -857,7 +876,12 @@ GGML_API int mi_llama_decode(struct mi_llama * m, int seq, const int32_t * token
         for (int j = 0; j < m->swa_size; j++) if (cp[j] >= 0) used_max_p1 = j + 1;
         n_kv_swa = std::min(m->swa_size, std::max(kv_pad, (int) GGML_PAD(used_max_p1, kv_pad)));
     }
-    auto key = std::make_tuple(seq, n_tokens, n_kv, n_kv_swa);
+    // MI_HARNESS_REUSE_GRAPH=1 (tests): llama.cpp rebuilds a graph in the same buf_compute_meta and lets ggml-alloc place it in the same compute buffer, so
+    // from one n_kv bucket to the next the backend sees the same node objects at the same addresses with other shapes; this harness otherwise builds a
+    // graph of its own, every tensor in memory of its own, per n_kv. In this mode one graph per (seq, n_tokens) is built for n_kv = n_ctx (the window cache:
+    // its size) — the worst-case reservation — and the n_kv-dependent tensors (masks, K / V views, their permutes, the K.q scores) are resized in place.
+    const bool reuse = getenv("MI_HARNESS_REUSE_GRAPH") && atoi(getenv("MI_HARNESS_REUSE_GRAPH")) != 0;
+    auto key = reuse ? std::make_tuple(seq, n_tokens, -1, -1) : std::make_tuple(seq, n_tokens, n_kv, n_kv_swa);
     auto it = m->graphs.find(key);
     if (it == m->graphs.end()) {
         if (m->graphs.size() >= 6*m->n_past.size()) {   // bound the number of live compute buffers
@@ -867,9 +891,10 @@ GGML_API int mi_llama_decode(struct mi_llama * m, int seq, const int32_t * token
             free_graph(victim->second);
             m->graphs.erase(victim);
         }
-        it = m->graphs.emplace(key, build_graph(m, seq, n_tokens, n_kv, n_kv_swa)).first;
+        it = m->graphs.emplace(key, reuse ? build_graph(m, seq, n_tokens, hp.n_ctx, m->swa_size) : build_graph(m, seq, n_tokens, n_kv, n_kv_swa)).first;
     }
     graph_inst & g = it->second;
+    if (reuse) set_graph_n_kv(g, n_kv, n_kv_swa);
     g.last_use = ++m->tick;
 
     // ---- set_inputs (src/llama-graph.cpp:16-58, src/llama-kv-cache-unified.cpp:1219-1400) through pinned staging

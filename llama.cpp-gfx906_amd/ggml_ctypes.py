@@ -65,7 +65,8 @@ class ggml_init_params(C.Structure):
 class mi355x_counters(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in (
         "graphs_computed", "nodes_computed", "kernels_launched", "graph_replays", "graph_captures", "mmvq_launches",
-        "mmq_launches", "weight_bytes", "act_quant_launches", "act_quant_reused", "split_mul_mats")]
+        "mmq_launches", "weight_bytes", "act_quant_launches", "act_quant_reused", "split_mul_mats",
+        "graph_partial_replays", "moe_combine_direct")]
 
 
 class mi355x_prof_entry(C.Structure):

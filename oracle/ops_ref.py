@@ -159,3 +159,27 @@ def mul_mat_dense(a, b):
         for i2 in range(b.shape[1]):
             out[i3, i2] = b[i3, i2] @ a[i3 // r3, i2 // r2].T
     return out
+
+
+def flash_attn_ext(q, K, V, mask, scale, max_bias=0.0, softcap=0.0, sinks=None):
+    """FLASH_ATTN_EXT (ggml_compute_forward_flash_attn_ext_f16, ggml/src/ggml-cpu/ops.cpp) in float64: q [T, n_head, hd], K / V the dequantized cache
+    [n_kv, n_head_kv, hd], mask [>= T, n_kv] (the f32 values of the f16 mask), sinks [n_head] or None -> [T, n_head, hd]. ALiBi: head h's mask
+    times its slope; the soft-cap: scale / c, then c * tanh."""
+    T, n_head, hd = q.shape
+    n_head_kv = K.shape[1]
+    n2 = 1 << int(np.floor(np.log2(n_head)))
+    m0, m1 = 2.0 ** (-max_bias / n2), 2.0 ** (-(max_bias / 2.0) / n2)
+    out = np.zeros((T, n_head, hd))
+    for h in range(n_head):
+        hk = h // (n_head // n_head_kv)
+        slope = 1.0 if max_bias <= 0 else (m0 ** (h + 1) if h < n2 else m1 ** (2 * (h - n2) + 1))
+        s = q[:, h, :].astype(np.float64) @ K[:, hk, :].T * scale
+        if softcap:
+            s = softcap * np.tanh(s / softcap)
+        s = s + slope * mask[:T].astype(np.float64)
+        mx = s.max(-1, keepdims=True)
+        if sinks is not None:
+            mx = np.maximum(mx, sinks[h])
+        p = np.exp(s - mx); den = p.sum(-1, keepdims=True) + (np.exp(sinks[h] - mx) if sinks is not None else 0.0)
+        out[:, h, :] = (p / den) @ V[:, hk, :]
+    return out

@@ -634,21 +634,7 @@ def test_flash_attn_ext_cache_types_alibi_softcap(hd, n_head, n_head_kv, n_kv, T
         be.compute(graph)                                                          # (the conversion buffer and any captured graph are reused)
         assert np.array_equal(got, gg.tensor_get(fa))
     K = Kf[:n_kv].reshape(n_kv, n_head_kv, hd); V = Vf[:n_kv].reshape(n_kv, n_head_kv, hd)
-    n2 = 1 << int(np.floor(np.log2(n_head)))
-    m0, m1 = 2.0 ** (-max_bias / n2), 2.0 ** (-(max_bias / 2.0) / n2)
-    exp = np.zeros((T, n_head, hd))
-    for h in range(n_head):
-        hk = h // (n_head // n_head_kv)
-        slope = 1.0 if max_bias <= 0 else (m0 ** (h + 1) if h < n2 else m1 ** (2 * (h - n2) + 1))
-        s = q_[0, :, h, :].astype(np.float64) @ K[:, hk, :].T * scale
-        if softcap:
-            s = softcap * np.tanh(s / softcap)
-        s = s + slope * mask[0, 0, :T].astype(np.float64)
-        mx = s.max(-1, keepdims=True)
-        if sinks:
-            mx = np.maximum(mx, sk[h])
-        p = np.exp(s - mx); den = p.sum(-1, keepdims=True) + (np.exp(sk[h] - mx) if sinks else 0.0)
-        exp[:, h, :] = (p / den) @ V[:, hk, :]
+    exp = ref.flash_attn_ext(q_[0], K, V, mask[0, 0], scale, max_bias, softcap, sk if sinks else None)
     assert got[0].shape == exp.shape
     assert orc.nmse(exp, got[0]) <= 5e-4, orc.nmse(exp, got[0])
 

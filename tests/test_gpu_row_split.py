@@ -52,7 +52,7 @@ def worker():
     assert not L.ggml_backend_dev_supports_buft(L.ggml_backend_reg_dev_get(be.reg, 1), equal)   # the main device's backend runs the graph
     assert not fn(5, (C.c_float * 16)())                                                   # no such device
 
-    def mul_mat(buft, qt, w, x, m, k, check_probe=False):
+    def mul_mat(buft, qt, w, x, m, k, check_probe=False, btype=gg.F32):
         n = x.shape[0]
         with gg.Context() as wc, gg.Context() as ctx:
             a = wc.new_tensor(qt, [k, m], "a")
@@ -62,7 +62,7 @@ def worker():
                 wc.buffers.append(buf)
             else:
                 assert wc.alloc(be)
-            b = ctx.new_tensor(gg.F32, [k, n], "b")
+            b = ctx.new_tensor(btype, [k, n], "b")
             guard0 = ctx.new_tensor(gg.F32, [1024], "g0")
             out = L.ggml_mul_mat(ctx.ctx, a, b)
             guard1 = ctx.new_tensor(gg.F32, [1024], "g1")
@@ -104,6 +104,22 @@ def worker():
                 assert orc.nmse(orc.mul_mat_2d(w, qt, x, "exact"), got) <= 5e-4
                 assert be.counters()["split_mul_mats"] == 4
     print("op level:", n_split, "split mat-muls match the unsplit ones")
+
+    # F16 activations on split weights (supports_op accepts them for any quantized MUL_MAT, tests/test-backend-ops.cpp:5715-5716): converted to F32
+    # on the main device first, as the unsplit path does; checked against the oracle as test_mul_mat_f16_src1 checks that path
+    from test_gpu_mul_mat import check
+    for tname in ("q4_K", "q6_K", "q5_K", "q8_0", "q4_0", "mxfp4"):
+        qt = QTYPES[tname]
+        for (m, k) in ((300, 1024), (32, 512)):
+            w = orc.random_blocks(rng, qt, (m,), k)
+            for n in (1, 3, 40):
+                x16 = rng.uniform(-1, 1, size=(n, k)).astype(np.float16)
+                be.reset_counters()
+                for shares in ([0.0] * 16, [3.0, 1.0]):
+                    got = mul_mat(split_buft(shares), qt, w, x16, m, k, btype=gg.F16)
+                    check(qt, w, x16.astype(np.float32), got)
+                assert be.counters()["split_mul_mats"] == 2
+    print("op level: F16 activations on split weights match the oracle")
 
     # ---- a whole model: every 2-D weight matrix split over the two devices, the rest (norms, KV cache, graph) on the main one
     for ftype in ("Q4_K_M", "Q8_0"):
