@@ -4,8 +4,8 @@
 // ggml/src/ggml-backend-impl.h is absent from the reference tree; field order is
 // ABI and MUST be verified against a real checkout before claiming drop-in
 // (a one-field mismatch is a crash, not a wrong number). Everything that depends
-// on these layouts lives in ONE translation unit of the backend
-// (llama.cpp-gfx906_amd/csrc/backend.cpp).
+// on these layouts lives in the backend*.cpp translation units of the backend
+// (llama.cpp-gfx906_amd/csrc/backend*.cpp).
 #pragma once
 
 #include "ggml-backend.h"

@@ -3,7 +3,7 @@
 
 Outputs (git-ignored, but they travel to the GPU box with the gpurun snapshot):
   lib/libggml-base-compat.so   harness stand-in for libggml-base (csrc/compat/ggml-compat.cpp)
-  lib/libggml-mi355x.so        THE PRODUCT: the ggml backend (csrc/backend.cpp + csrc/*.hip)
+  lib/libggml-mi355x.so        THE PRODUCT: the ggml backend (csrc/backend*.cpp + csrc/*.hip)
   lib/libmi355x-harness.so     synthetic llama graph driver used by bench.py/tests (csrc/harness/*.cpp)
 """
 import os
@@ -31,6 +31,9 @@ KERNEL_SRCS = ["quantize_act.hip", "mmvq.hip", "mmvq_cols_mfma.hip", "mmq.hip", 
                # the persistent grouped mat-vec, one translation unit per weight format (they compile in parallel)
                "mmvq_fused_q4_K.hip", "mmvq_fused_q5_K.hip", "mmvq_fused_q6_K.hip", "mmvq_fused_q8_0.hip", "mmvq_fused_q4_0.hip", "mmvq_fused_mxfp4.hip",
                "mmvq_fused_q4_K_q5_K.hip", "mmvq_fused_q4_K_q6_K.hip", "mmvq_fused_q5_K_q6_K.hip", "mmvq_fused_q8_0_q4_K.hip"]
+
+# the host side: the only translation units that see ggml struct layouts (compiled as HIP for the runtime's headers)
+BACKEND_SRCS = ["backend.cpp", "backend_nodes.cpp", "backend_graph.cpp"]
 
 
 def run(cmd):
@@ -66,19 +69,21 @@ def build(verbose=True):
         jobs.append(ex.submit(compile_obj, CSRC / "compat" / "ggml-compat.cpp", ["-x", "c++"]))
         for s in KERNEL_SRCS:
             jobs.append(ex.submit(compile_obj, CSRC / s, HIPFLAGS))
-        jobs.append(ex.submit(compile_obj, CSRC / "backend.cpp", ["-x", "hip", *HIPFLAGS]))
+        for s in BACKEND_SRCS:
+            jobs.append(ex.submit(compile_obj, CSRC / s, ["-x", "hip", *HIPFLAGS]))
         harness_srcs = sorted((CSRC / "harness").glob("*.cpp")) if (CSRC / "harness").exists() else []
         for s in harness_srcs:
             jobs.append(ex.submit(compile_obj, s, ["-x", "c++"]))
         objs = [j.result() for j in jobs]
-    compat_o, kern_o, backend_o, harness_o = objs[0], objs[1:1 + len(KERNEL_SRCS)], objs[1 + len(KERNEL_SRCS)], objs[2 + len(KERNEL_SRCS):]
+    nk, nb = len(KERNEL_SRCS), len(BACKEND_SRCS)
+    compat_o, kern_o, backend_o, harness_o = objs[0], objs[1:1 + nk], objs[1 + nk:1 + nk + nb], objs[1 + nk + nb:]
 
     base = LIB / "libggml-base-compat.so"
     if newer([compat_o], base):
         run([HIPCC, "-shared", "-o", str(base), str(compat_o), "-ldl"])
     be = LIB / "libggml-mi355x.so"
-    if newer([*kern_o, backend_o, base], be):
-        run([HIPCC, "-shared", f"--offload-arch={ARCH}", "-fno-gpu-rdc", "-o", str(be), *map(str, kern_o), str(backend_o),
+    if newer([*kern_o, *backend_o, base], be):
+        run([HIPCC, "-shared", f"--offload-arch={ARCH}", "-fno-gpu-rdc", "-o", str(be), *map(str, kern_o), *map(str, backend_o),
              "-L", str(LIB), "-lggml-base-compat", "-Wl,-rpath,$ORIGIN"])
     if harness_o:
         hz = LIB / "libmi355x-harness.so"

@@ -1,0 +1,207 @@
+// backend_impl.h — internal to the backend*.cpp translation units (the only ones that see ggml struct layouts): error macros, the backend
+// context, the per-pass state, the graph cache entry, small shared helpers and the few functions that cross files.
+//   backend.cpp        registry, device, buffer types, the backend vtable, uploads, copies, events, supports_op, options, profile, C exports
+//   backend_nodes.cpp  the pass state's operations, op launchers, fusion matchers, compute_node
+//   backend_graph.cpp  node signatures, the hipGraph cache, segmented capture and replay, prepare_buffers, graph_compute
+#pragma once
+
+#include "ggml-mi355x.h"
+#include "ggml-backend-impl.h"
+#include "ggml-impl.h"
+
+#include "kernels.h"
+
+#include <hip/hip_runtime.h>
+
+#include <stddef.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include <string>
+#include <unordered_map>
+#include <vector>
+
+using namespace mi355x;
+
+#define MI_CHECK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { \
+    GGML_ABORT("MI355X backend: HIP error %s (%s) at %s:%d", hipGetErrorName(e_), hipGetErrorString(e_), __FILE__, __LINE__); } } while (0)
+
+#define MI_LOG(...) do { fprintf(stderr, "ggml-mi355x: " __VA_ARGS__); } while (0)
+
+// On the graph path (be_graph_compute and what it calls) a HIP error is not fatal: it unwinds to be_graph_compute, which ends a capture in
+// progress and returns GGML_STATUS_FAILED — llama_context::decode maps that and rolls the KV cells of the batch back
+// (src/llama-context.cpp:1078-1107). Everywhere else (buffer and device entry points, which have no status to return) MI_CHECK aborts.
+struct mi_graph_error { hipError_t err; const char * file; int line; };
+#define MI_CHECK_G(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) throw mi_graph_error{ e_, __FILE__, __LINE__ }; } while (0)
+#define MI_REQUIRE_G(cond) do { if (!(cond)) throw mi_graph_error{ hipErrorInvalidValue, __FILE__, __LINE__ }; } while (0)
+
+// ---- device table ----
+struct mi_device {
+    int id;
+    std::string name;         // "MI355X0"
+    std::string description;
+    size_t total_mem;
+    struct ggml_backend_device dev;
+    struct ggml_backend_buffer_type buft;
+};
+
+struct mi_globals {
+    int n_devices = 0;
+    mi_device devices[GGML_MI355X_MAX_DEVICES];
+    struct ggml_backend_reg reg;
+    struct ggml_backend_buffer_type host_buft;
+    bool initialised = false;
+};
+
+mi_globals & G();
+
+static inline void set_device(int id) { MI_CHECK(hipSetDevice(id)); }
+
+struct mi_split_tensor {                                   // tensor->extra of a tensor in a split buffer
+    void *  data[GGML_MI355X_MAX_DEVICES] = {};            // the slice in device i's memory (NULL: no rows there)
+    int64_t row_lo[GGML_MI355X_MAX_DEVICES + 1] = {};      // device i holds rows [row_lo[i], row_lo[i+1])
+};
+
+// ---- the hipGraph cache entry ----
+// What must be unchanged for a captured hipGraph to be replayed, per node (the checks the reference's GPU
+// backends make before reusing a captured graph): the node itself, its op/type/shape/strides/data pointer,
+// a hash of op_params, and the data pointers + leading shape of its sources (leaf tensors are not nodes and
+// split graphs carry no leaf list, so their placement is pinned through the nodes that read them).
+struct node_sig {
+    const void * node; const void * data;
+    const void * src[GGML_MAX_SRC];                                            // the source TENSORS: the graph's topology (checked for the whole graph before any segment is launched)
+    int32_t op, type;
+    int64_t ne[4]; size_t nb[3];
+    const void * src_data[GGML_MAX_SRC]; uint32_t src_hash[GGML_MAX_SRC];      // every source: placement + a hash of its type, shape and strides
+    uint32_t params_hash; uint32_t flags;
+};
+
+static_assert(sizeof(node_sig) == 16 + 8*GGML_MAX_SRC + 8 + 32 + 24 + 8*GGML_MAX_SRC + 4*GGML_MAX_SRC + 8, "node_sig has no padding bytes: signatures are compared with memcmp");
+struct graph_seg { int begin, end; hipGraphExec_t exec; };      // nodes [begin, end) as one executable graph (exec == NULL: view ops only, nothing to launch)
+struct graph_entry {
+    std::vector<node_sig> sig; uint64_t digest = 0;      // digest: a cheap hash of the signature — only the entry that shares it is compared in full
+    std::vector<graph_seg> segs;                          // empty: not captured (yet)
+    uint64_t last_use = 0;
+    int seen = 0;              // identical submissions observed (capture on the 2nd)
+};
+
+// ---- per-pass state ----
+// What one node of a pass over a graph (run_nodes, eager or under capture) leaves for a later node of the same pass. The buffers it points into
+// (scratch, moe_ws, rope_tab) belong to mi_backend_ctx; this only says what they hold. Every reset or invalidation goes through the operations below.
+struct mi_pass {
+    std::unordered_map<const struct ggml_tensor *, int> uses;   // consumers per tensor in the graph being run (fusion legality)
+    // the activations of a quantized mat-mul as the scratch holds them (quantized, or the bf16 copy the MFMA prefill kernel reads); off: where in the
+    // scratch the bf16 copy sits (a producer kernel that still reads offset 0 writes its result's copy higher up). Nodes lo..hi are the launch that
+    // produced it (empty when a node quantized its own input): their writes over `data` do not end it, anybody else's do.
+    struct { const void * data; int64_t k, n_inner, n_outer; size_t s_inner, s_outer; int kind; act_q8 q; bool valid; size_t span;
+             size_t off; int lo = 0, hi = -1; } aq = {};
+    // the last router launch: it ranked `vals` (probabilities, or logits) into `sorted` and left the eight best values in rank order at moe_ws + 64
+    // (floats the kernel does not use otherwise): a combine that gathers vals[sorted[u]] takes them from there — one load instead of two dependent cold ones.
+    // Keyed on addresses, so any later node that writes over vals or sorted (an allocator reuses a dead router's memory for the next layer's, whose router
+    // may run unfused) ends it; nodes lo..hi are the router launch's own.
+    struct { bool valid = false; const void * vals = nullptr; const void * sorted = nullptr; size_t bytes = 0; int lo = 0, hi = -1; } rt;
+    // a MoE combine left pending (try_fused_moe_combine): the vector x_out = res + sum_u w_u * plane u does not exist until the launch that reads it (the next
+    // norm + mat-vec launch, streamed kernel) has evaluated it in its prologue, or pp_flush has
+    struct { bool active = false; const float * res = nullptr; float * x_out = nullptr; int n_planes = 0; int64_t m = 0;
+             const float * planes = nullptr; int stride = 0;                                     // where the planes are (floats between them)
+             const float * probs = nullptr; size_t probs_bytes = 0; const int32_t * ids = nullptr; int mode = 0; } pp;      // planes = the used experts' outputs, weights from probs[ids[u]]
+    // rope_tab holds the rotation table for these parameters ((cos, sin) per pair index; mmvq_rope::table): filled by one small launch when a pass's
+    // first rotated mat-vec launch comes up (and again if a launch asks for other rope parameters), read by every such launch after it
+    mmvq_rope rope_key = {}; bool rope_valid = false;
+
+    void begin(const struct ggml_cgraph * g, bool count_uses);         // a pass starts: nothing is carried over from the last one
+    // a capture segment ends. aq does not cross a cut: the scratch it describes may be replaced (prepare_buffers) before a partial replay runs the
+    // rest of a graph behind a launched prefix. rt and the rope table do: they describe moe_ws and rope_tab, allocated once and never replaced, and
+    // the prefix launched in front of a cut is the one this graph's own capture holds, so it has left the same values there.
+    void cut() { aq.valid = false; }
+    void abandon() { aq.valid = false; pp.active = false; }            // a pass unwound by an error
+    void drop_act() { aq.valid = false; }                              // a launch reuses the scratch
+    void note_writes(const struct ggml_cgraph * g, int i, int n);      // nodes [i, i+n) have run: what they wrote over ends aq / rt
+};
+
+struct mi_backend_ctx {
+    int device;                    // HIP device id
+    int dev_index = 0;             // index into G().devices
+    std::string name;
+    hipStream_t stream = nullptr;
+
+    void * scratch = nullptr;      // quantized activations
+    size_t scratch_size = 0;
+    int moe_dual = -1;                  // option "moe_dual"
+    float * moe_ws = nullptr;                                   // logits + arrival counter of the multi-workgroup router kernel (moe_route); the router hand-off at + 64
+    // producer-side activation quantization (mmvq_fin): the image a GLU launch writes for the mat-vec that follows + its arrival counters
+    void * fin_img = nullptr; unsigned * fin_cnt = nullptr;
+    float * rope_tab = nullptr;                                 // the rotation table of the token being decoded (mi_pass::rope_valid)
+    static constexpr size_t FIN_IMG_BYTES = 64*1024; static constexpr int FIN_COUNTERS = 256;
+    void * cvt = nullptr; size_t cvt_size = 0;                  // the F32 copy of an F16 src1 of a quantized MUL_MAT
+    void * kv16 = nullptr; size_t kv16_size = 0;                // FLASH_ATTN_EXT: dense f16 copies of a quantized / bf16 cache view, and the transposed V of the prefill kernel (kv_to_f16)
+    float * attn_part = nullptr; size_t attn_part_bytes = 0;   // partial results of the decode attention's cell ranges at long contexts (attn_decode)
+
+    mi_pass pass;
+
+    // hipGraph cache (one entry: llama.cpp re-submits the same decode graph, src/llama-context.cpp:728)
+    bool use_graphs = true;
+    bool use_fusion = true;
+    std::vector<graph_entry> graphs;     // small LRU: decode graphs differ only in n_kv (one per 32 tokens of context)
+    std::vector<node_sig> cur_sig; uint64_t cur_digest = 0;
+    uint64_t graph_tick = 0;
+
+    struct ggml_backend_mi355x_counters cnt = {};
+
+    bool capturing = false;
+    graph_entry * cap_entry = nullptr;               // the cache entry a capture in progress fills (dropped if the capture fails)
+    // small uploads (set_tensor_async of <= UP_SMALL_MAX bytes: a decode step's inputs) are staged in a pinned, device-mapped ring and go out as ONE
+    // launch in front of whatever the stream is asked to do next (uploads_flush), instead of one copy each
+    struct { char * host = nullptr; char * dev = nullptr; int cur = 0; size_t off = 0; hipEvent_t ev[2] = { nullptr, nullptr }; bool ev_pending[2] = { false, false };
+             int n = 0; upload_batch b = {}; bool failed = false; } up;
+    static constexpr size_t UP_HALF = 1u << 20, UP_SMALL_MAX = 64u << 10;
+    unsigned * err_host = nullptr;                   // host-mapped words: a bounded wait inside a kernel gave up ([1] the MoE router)
+    unsigned * err_dev = nullptr;                    // ... their device address
+
+    // "profile" option: every quantized mat-mul launch is bracketed by a hipEvent pair on this stream (eager mode)
+    struct prof_rec { int type; int64_t m, k, n; uint64_t bytes; hipEvent_t e0, e1; const char * kernel = nullptr; };
+    bool profiling = false;
+    bool prof_in_graph = false;      // option "profile" = 2: the event pairs are captured into the hipGraphs as event-record nodes
+    bool prof_suspend = false;       //   ... and eager passes (before a graph's capture) are not recorded
+    std::vector<prof_rec> prof;
+    std::vector<hipEvent_t> ev_pool;
+
+    // row-split mat-muls: a stream, a completion event and (for the many-token kernel) a scratch area per peer device, made on first use
+    struct split_peer { hipStream_t stream = nullptr; hipEvent_t done = nullptr; void * scratch = nullptr; size_t scratch_size = 0; };
+    split_peer peers[GGML_MI355X_MAX_DEVICES];
+    hipEvent_t split_ready = nullptr;
+    hipEvent_t cpy_ev = nullptr;     // cpy_tensor_async to another backend: the destination stream waits on it
+    bool split_graph = false;        // the graph being run reads row-split weights: eager execution (several devices' streams take part)
+};
+
+// ---- small shared helpers ----
+static inline bool is_view_op(enum ggml_op op) {
+    return op == GGML_OP_NONE || op == GGML_OP_RESHAPE || op == GGML_OP_VIEW || op == GGML_OP_PERMUTE || op == GGML_OP_TRANSPOSE;
+}
+static inline float op_f32(const struct ggml_tensor * t, int i) { float f; memcpy(&f, &t->op_params[i], 4); return f; }
+static inline tensor_desc desc(const struct ggml_tensor * t) {
+    tensor_desc d;
+    d.data = t->data; d.type = (int) t->type;
+    for (int i = 0; i < 4; i++) { d.ne[i] = t->ne[i]; d.nb[i] = t->nb[i]; }
+    return d;
+}
+static inline bool ranges_overlap(const void * a, size_t na, const void * b, size_t nb) {
+    const char * pa = (const char *) a; const char * pb = (const char *) b;
+    return pa < pb + nb && pb < pa + na;
+}
+
+// ---- across files ----
+// backend.cpp
+bool tensor_is_split(const struct ggml_tensor * t);
+void uploads_flush(mi_backend_ctx * c);
+void prof_begin(mi_backend_ctx * c, int type, int64_t m, int64_t k, int64_t n, uint64_t bytes);
+void prof_end(mi_backend_ctx * c);
+void prof_set_hooks(mi_backend_ctx * c);      // (re)install this backend's launch hooks of the grouped mat-vec module for the calling thread
+// backend_nodes.cpp
+int  compute_node(mi_backend_ctx * c, struct ggml_cgraph * g, int i);     // returns the number of graph nodes consumed (>= 1)
+void pass_end(mi_backend_ctx * c);                                         // the last node of a pass has run: the pending combine runs, aq ends
+void fa_kv16_plan(const struct ggml_tensor * n, size_t & k_bytes, size_t & v_bytes);
+// backend_graph.cpp
+enum ggml_status be_graph_compute(ggml_backend_t backend, struct ggml_cgraph * g);
+void drop_graphs(mi_backend_ctx * c);

@@ -1,6 +1,6 @@
 // kernels.h — host-callable launchers for the gfx950 kernels. Plain pointers,
 // strides in BYTES (ggml nb[] convention) and a hipStream_t; no ggml types, so the
-// kernels can be driven from backend.cpp (ggml tensors) or from the flat C-ABI in
+// kernels can be driven from backend*.cpp (ggml tensors) or from the flat C-ABI in
 // include/ggml-mi355x.h. Every launcher is asynchronous on `stream` and performs
 // no allocation or synchronisation (safe under hipGraph capture).
 #pragma once
@@ -102,7 +102,7 @@ void   mul_mat_q_id(int type_a, const void * W, size_t w_row_stride, size_t w_ex
                     const float * b, size_t b_nb1, size_t b_nb2, int64_t n_b,
                     const int32_t * ids, size_t ids_nb0, size_t ids_nb1, int64_t n_used, int64_t n_tokens, int64_t n_expert,
                     void * scratch, float * dst, size_t dst_nb1, size_t dst_nb2, hipStream_t stream);
-// The pieces of the above, for the fused expert chain of a prompt pass (backend.cpp try_fused_prefill_moe): one sort and one bf16 copy of the layer input serve
+// The pieces of the above, for the fused expert chain of a prompt pass (backend_nodes.cpp try_fused_prefill_moe): one sort and one bf16 copy of the layer input serve
 // gate, up and down; gate / up run as ONE dual launch with the ADD_ID biases and the (oai) SwiGLU in its epilogue and hand the down projection bf16 rows per pair;
 // the down launch adds its ADD_ID bias and multiplies with the routing weight (MUL(experts, weights), src/llama-graph.cpp:990)
 struct mmq_moe_epi { const float * bias = nullptr; const float * bias2 = nullptr; size_t bias_stride = 0; const float * scale = nullptr; size_t scale_nb0 = 0, scale_nb1 = 0;

@@ -359,7 +359,7 @@ def test_mul_mat_id_prefill_grouped(name, n_mats, n_used, bcast_b, n, m, k):
 ])
 def test_moe_expert_chain_many_tokens(gname, dname, n_mats, n_used, n, m, k, biased, oai, weighted):
     """The experts of build_moe_ffn for a prompt pass (src/llama-graph.cpp:914-990): MUL_MAT_ID(up) [ADD_ID]; MUL_MAT_ID(gate) [ADD_ID]; swiglu | swiglu_oai;
-    MUL_MAT_ID(down) [ADD_ID] [MUL weights]. With fusions on this is one copy, one dual tile launch and one down launch (+ a sort each) (backend.cpp try_fused_prefill_moe);
+    MUL_MAT_ID(down) [ADD_ID] [MUL weights]. With fusions on this is one copy, one dual tile launch and one down launch (+ a sort each) (backend_nodes.cpp try_fused_prefill_moe);
     with fusions off, node by node. Both against the exact product of the dequantized weights (bf16 operands: the MUL_MAT_ID gate), and against each other:
     the fused chain rounds the same values to bf16 at the same places, so only the ragged last digits of expf differ."""
     rng = np.random.default_rng(500 + n)
@@ -414,7 +414,7 @@ def test_moe_expert_chain_many_tokens(gname, dname, n_mats, n_used, n, m, k, bia
 @pytest.mark.parametrize("name,k", [("q8_0", 320), ("q4_K", 512)])
 def test_prompt_pass_qkv_with_bias_rows(name, k):
     """gpt-oss's attention projections in a prompt pass (src/llama-model.cpp:17636-17645): MUL_MAT(wq) + bq, MUL_MAT(wk) + bk, MUL_MAT(wv) + bv on the same 512
-    tokens. Fused: ONE grouped launch (k = 2880 does not split, 80 tiles) with the bias rows added in its epilogue (backend.cpp try_fused_prefill_qkv); node by node:
+    tokens. Fused: ONE grouped launch (k = 2880 does not split, 80 tiles) with the bias rows added in its epilogue (backend_nodes.cpp try_fused_prefill_qkv); node by node:
     three launches and three ADDs. Same operands, same order of accumulation: the same bits; and the exact product within the MUL_MAT gate."""
     rng = np.random.default_rng(31)
     qt = QTYPES[name]; n = 512; ms = (4096, 512, 512)
@@ -444,7 +444,7 @@ def test_prompt_pass_qkv_with_bias_rows(name, k):
 @pytest.mark.parametrize("n_used,with_res", [(2, True), (4, True), (4, False), (8, True)])
 def test_moe_slot_sum_many_tokens(n_used, with_res):
     """The end of build_moe_ffn for a prompt pass (src/llama-graph.cpp:996-1012 + the residual ADD of src/llama-model.cpp:6096): the ADD chain over the slot views of
-    the experts' outputs, fused into one pass (backend.cpp try_fused_slot_sum) — bit-identical to node-by-node execution, same order of additions."""
+    the experts' outputs, fused into one pass (backend_nodes.cpp try_fused_slot_sum) — bit-identical to node-by-node execution, same order of additions."""
     rng = np.random.default_rng(900 + n_used)
     m, n = 320, 37
     ex_ = rng.uniform(-1, 1, size=(1, n, n_used, m)).astype(np.float32); res_ = rng.uniform(-1, 1, size=(1, 1, n, m)).astype(np.float32)
