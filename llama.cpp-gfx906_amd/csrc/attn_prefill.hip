@@ -285,7 +285,7 @@ void attn_prefill(const void * q, size_t q_nb1, size_t q_nb2, const void * k, si
     // few workgroups (short prompts): the waves of a (head, query tile) split the cell blocks of an iteration two or four ways, shortening the loop that is the critical path
     const int64_t wgs1 = ((T + 32*(APF_NW/hpw) - 1)/(32*(APF_NW/hpw)))*(n_head/hpw);
     int ksp = (hpw <= 4 && wgs1 < 160 && n_kv >= 128) ? 2 : 1;
-    static const bool ks4_on = !getenv("GGML_MI355X_ATTN_PF_KS4") || atoi(getenv("GGML_MI355X_ATTN_PF_KS4")) != 0;
+    static const bool ks4_on = env_on("GGML_MI355X_ATTN_PF_KS4");
     if (ks4_on && ksp == 2 && R % 2 == 0 && n_kv >= 256 && head_dim == 128 && v_trans) {
         // ... four ways with two heads per workgroup when even the pairs leave half the chip idle (pp512 of a 32-head model: 128 workgroups -> 256)
         const int64_t wgs2 = ((T + 32*(APF_NW/(hpw*2)) - 1)/(32*(APF_NW/(hpw*2))))*(n_head/hpw);

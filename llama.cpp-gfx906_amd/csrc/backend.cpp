@@ -300,36 +300,17 @@ static hipEvent_t prof_event(mi_backend_ctx * c) {
     if (!c->ev_pool.empty()) { hipEvent_t e = c->ev_pool.back(); c->ev_pool.pop_back(); return e; }
     hipEvent_t e; MI_CHECK(hipEventCreate(&e)); return e;
 }
-void prof_begin(mi_backend_ctx * c, int type, int64_t m, int64_t k, int64_t n, uint64_t bytes) {
+// record_start = false: the pair is only made — the caller hands it to a launch that carries it as its dispatch's own start / stop events
+void prof_begin(mi_backend_ctx * c, int type, int64_t m, int64_t k, int64_t n, uint64_t bytes, bool record_start) {
     if (!c->profiling || c->prof_suspend) return;
     mi_backend_ctx::prof_rec r = { type, m, k, n, bytes, prof_event(c), prof_event(c) };
-    MI_CHECK(hipEventRecord(r.e0, c->stream));
+    if (record_start) MI_CHECK(hipEventRecord(r.e0, c->stream));
     c->prof.push_back(r);
 }
 void prof_end(mi_backend_ctx * c) {
     if (!c->profiling || c->prof_suspend) return;
     MI_CHECK(hipEventRecord(c->prof.back().e1, c->stream));
 }
-// the grouped mat-vec module launches (possibly several graph nodes later, possibly several launches merged into one): it calls back
-static void prof_hook_pre(void * ctx, int type, uint64_t wbytes, int n_merged, int64_t k) {
-    // m < 0: grouped launch, |m| = KiB of weights; n = launches merged into this kernel
-    mi_backend_ctx * c = (mi_backend_ctx *) ctx;
-    if (!c->profiling || c->prof_suspend) return;
-    if (c->prof_in_graph) { prof_begin(c, type, -(int64_t)(wbytes/1024), k, n_merged, wbytes); return; }
-    // eager: the pair rides on the dispatch itself (kernel start -> kernel end, the interval rocprofv3's kernel trace reports)
-    mi_backend_ctx::prof_rec r = { type, -(int64_t)(wbytes/1024), k, n_merged, wbytes, prof_event(c), prof_event(c) };
-    mul_mat_vec_q_fused_set_launch_events(r.e0, r.e1);
-    c->prof.push_back(r);
-}
-static void prof_hook_post(void * ctx, int, uint64_t, int, int64_t) {
-    mi_backend_ctx * c = (mi_backend_ctx *) ctx;
-    if (!c->profiling || c->prof_suspend) return;
-    if (c->prof_in_graph) prof_end(c);
-    c->prof.back().kernel = mul_mat_vec_q_fused_last_kernel();
-}
-// the grouped mat-vec module keeps its launch hooks per host thread
-void prof_set_hooks(mi_backend_ctx * c) { mul_mat_vec_q_fused_set_hooks(c->profiling ? prof_hook_pre : nullptr, c->profiling ? prof_hook_post : nullptr, c); }
-
 
 static ggml_guid_t mi_guid(void) {
     static ggml_guid guid = { 0x4d, 0x49, 0x33, 0x35, 0x35, 0x58, 0x67, 0x66, 0x78, 0x39, 0x35, 0x30, 0x63, 0x64, 0x6e, 0x34 };
@@ -407,7 +388,7 @@ static void be_set_tensor_async(ggml_backend_t backend, struct ggml_tensor * ten
     mi_backend_ctx * c = (mi_backend_ctx *) backend->context;
     set_device(c->device);
     if (size == 0) return;
-    static const bool batch = !getenv("GGML_MI355X_UPLOAD_BATCH") || atoi(getenv("GGML_MI355X_UPLOAD_BATCH")) != 0;
+    static const bool batch = env_on("GGML_MI355X_UPLOAD_BATCH");
     if (batch && size <= mi_backend_ctx::UP_SMALL_MAX && uploads_stage(c, (char *) tensor->data + offset, data, size)) return;
     uploads_flush(c);       // stream order: what was set before this goes first
     MI_CHECK(hipMemcpyAsync((char *) tensor->data + offset, data, size, hipMemcpyHostToDevice, c->stream));
@@ -691,7 +672,7 @@ mi_globals & G() {
         g.host_buft = { mi_host_buft_iface, NULL, NULL };
         // GGML_MI355X_VIRTUAL_DEVICES=v lists every GPU v times (same HIP device, separate backend / stream / buffer type each): lets the
         // multi-device paths (layer split in one process, row split) be exercised on a one-GPU box
-        const int virt = getenv("GGML_MI355X_VIRTUAL_DEVICES") ? std::max(1, atoi(getenv("GGML_MI355X_VIRTUAL_DEVICES"))) : 1;
+        const int virt = std::max(1, (int) env_int("GGML_MI355X_VIRTUAL_DEVICES", 1));
         for (int iv = 0; iv < n*virt && g.n_devices < GGML_MI355X_MAX_DEVICES; iv++) {
             const int i = iv/virt;
             hipDeviceProp_t prop;
@@ -778,8 +759,8 @@ ggml_backend_t ggml_backend_mi355x_init(int device) {
     c->dev_index = device;
     c->name = d.name;
     MI_CHECK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
-    if (const char * e = getenv("GGML_MI355X_GRAPHS")) c->use_graphs = atoi(e) != 0;
-    if (const char * e = getenv("GGML_MI355X_FUSION")) c->use_fusion = atoi(e) != 0;
+    c->use_graphs = env_on("GGML_MI355X_GRAPHS", c->use_graphs);
+    c->use_fusion = env_on("GGML_MI355X_FUSION", c->use_fusion);
     ggml_backend_t backend = new ggml_backend{ mi_guid(), mi_backend_iface, &d.dev, c };
     return backend;
 }
@@ -862,7 +843,6 @@ int ggml_backend_mi355x_set_option(ggml_backend_t backend, const char * key, int
         for (auto & r : c->prof) { c->ev_pool.push_back(r.e0); c->ev_pool.push_back(r.e1); }
         c->prof.clear();
         c->profiling = value != 0; c->prof_in_graph = value == 2; c->prof_suspend = false;
-        prof_set_hooks(c);
         return 0;
     }
     if (strcmp(key, "fusion") == 0) {

@@ -61,10 +61,9 @@ static void end_capture_segment(mi_backend_ctx * c, graph_entry & e, int begin, 
 
 // runs nodes [start, n_nodes). cap != NULL: under stream capture into cap's segments (the caller has begun the first capture; the last one is ended here)
 static void run_nodes(mi_backend_ctx * c, struct ggml_cgraph * g, int start = 0, graph_entry * cap = nullptr) {
-    prof_set_hooks(c);      // (for the thread that computes)
     c->pass.begin(g, c->use_fusion);
     // segment sizes in kernel launches: the first is small (the GPU starts early), the second covers the time the host needs to launch the rest
-    static const int seg_kernels[2] = { getenv("GGML_MI355X_GRAPH_SEG0") ? atoi(getenv("GGML_MI355X_GRAPH_SEG0")) : 6, getenv("GGML_MI355X_GRAPH_SEG1") ? atoi(getenv("GGML_MI355X_GRAPH_SEG1")) : 24 };
+    static const int seg_kernels[2] = { (int) env_int("GGML_MI355X_GRAPH_SEG0", 6), (int) env_int("GGML_MI355X_GRAPH_SEG1", 24) };
     int seg_begin = start; uint64_t k0 = c->cnt.kernels_launched;
     for (int i = start; i < g->n_nodes; ) {
         i += compute_node(c, g, i);
@@ -287,11 +286,12 @@ static enum ggml_status graph_compute_suffix(mi_backend_ctx * c, struct ggml_cgr
 
 static enum ggml_status be_graph_compute_impl(ggml_backend_t backend, struct ggml_cgraph * g);
 static double g_host_ns = 0.0; static long g_host_calls = 0;     // GGML_MI355X_HOST_TIMING=1: host time spent inside graph_compute
+static bool host_timing() { static const bool on = env_is_set("GGML_MI355X_HOST_TIMING"); return on; }
 enum ggml_status be_graph_compute(ggml_backend_t backend, struct ggml_cgraph * g) {
     mi_backend_ctx * c = (mi_backend_ctx *) backend->context;
     (void) hipGetLastError();      // a stale thread-level error (another library's probe, a failed allocation elsewhere) is not this graph's: only what this call raises counts
     try {
-        static const bool timing = getenv("GGML_MI355X_HOST_TIMING") != nullptr;
+        const bool timing = host_timing();
         const auto t0 = std::chrono::steady_clock::now();
         const enum ggml_status st = be_graph_compute_impl(backend, g);
         if (timing) {
@@ -328,7 +328,7 @@ static enum ggml_status be_graph_compute_impl(ggml_backend_t backend, struct ggm
     c->cnt.graphs_computed++;
     uploads_flush(c);       // the inputs the host has set (set_tensor_async) go out first, as one launch
 
-    static const bool timing2 = getenv("GGML_MI355X_HOST_TIMING") != nullptr;
+    const bool timing2 = host_timing();
     static double t_first = 0, t_rest = 0; static long n_rep = 0;
     const bool try_graph = c->use_graphs && (!c->profiling || c->prof_in_graph) && g->n_nodes >= 8;
 

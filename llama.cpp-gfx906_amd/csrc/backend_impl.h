@@ -195,9 +195,10 @@ static inline bool ranges_overlap(const void * a, size_t na, const void * b, siz
 // backend.cpp
 bool tensor_is_split(const struct ggml_tensor * t);
 void uploads_flush(mi_backend_ctx * c);
-void prof_begin(mi_backend_ctx * c, int type, int64_t m, int64_t k, int64_t n, uint64_t bytes);
+// option "profile": open / close the record of one quantized mat-mul launch (no-ops when the option is off). In a record, m < 0 marks a grouped
+// mat-vec launch: |m| = KiB of weights (emit_mmv, backend_nodes.cpp)
+void prof_begin(mi_backend_ctx * c, int type, int64_t m, int64_t k, int64_t n, uint64_t bytes, bool record_start = true);
 void prof_end(mi_backend_ctx * c);
-void prof_set_hooks(mi_backend_ctx * c);      // (re)install this backend's launch hooks of the grouped mat-vec module for the calling thread
 // backend_nodes.cpp
 int  compute_node(mi_backend_ctx * c, struct ggml_cgraph * g, int i);     // returns the number of graph nodes consumed (>= 1)
 void pass_end(mi_backend_ctx * c);                                         // the last node of a pass has run: the pending combine runs, aq ends

@@ -260,9 +260,20 @@ static void op_flash_attn_ext(mi_backend_ctx * c, struct ggml_tensor * node) {
     c->cnt.kernels_launched++;
 }
 
-static void emit_mmv(mi_backend_ctx * c, const mmvq_group * grp, int nc, int64_t K, const mmvq_input & in, const mmvq_rope * rope, const mmvq_fin * fin) {
-    mul_mat_vec_q_fused(grp, nc, K, in, rope, c->stream, fin);
-    c->cnt.kernels_launched++;
+// the one place that launches a grouped mat-vec. wbytes: the weight bytes the launch streams, as its caller counts them. Profile record: m < 0 marks a
+// grouped launch, |m| = KiB of weights; n = 1; type of the first group. Eager profiling: the event pair rides on the dispatch itself (kernel start ->
+// kernel end, the interval rocprofv3's kernel trace reports); in-graph profiling: event-record nodes around the call, like every other mat-mul — so
+// where the dispatcher first has to run a pending MoE combine as its own kernel (no streamed route), that kernel lies inside the pair.
+// (The type is the first group's on both routes, deliberately: the register-ring route once reported the lower type of a mixed launch.)
+static void emit_mmv(mi_backend_ctx * c, const mmvq_group * grp, int nc, int64_t K, const mmvq_input & in, const mmvq_rope * rope, const mmvq_fin * fin, uint64_t wbytes) {
+    const bool prof = c->profiling && !c->prof_suspend;
+    mmvq_launch_rec rec = { nullptr, nullptr, "" };
+    prof_begin(c, grp[0].type, -(int64_t)(wbytes/1024), K, 1, wbytes, c->prof_in_graph);
+    if (prof && !c->prof_in_graph) { rec.e0 = c->prof.back().e0; rec.e1 = c->prof.back().e1; }
+    mul_mat_vec_q_fused(grp, nc, K, in, rope, c->stream, fin, prof ? &rec : nullptr);
+    if (prof && c->prof_in_graph) prof_end(c);
+    if (prof) c->prof.back().kernel = rec.kernel;
+    c->cnt.mmvq_launches++; c->cnt.kernels_launched++; c->cnt.weight_bytes += wbytes;
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -523,7 +534,7 @@ static int try_fused_mmv(mi_backend_ctx * c, struct ggml_cgraph * g, int i, int 
     // gate/up/SwiGLU whose output the down projection reads next (build_ffn, src/llama-graph.cpp:691-748): the launch also writes the quantized
     // image of its output (mmvq_fin) — the f32 tensor is written as always, so any other reader still finds it
     mmvq_fin fin = {}; act_q8 fin_q = {}; const struct ggml_tensor * fin_t = nullptr;
-    static const bool fin_env = !getenv("GGML_MI355X_FIN") || atoi(getenv("GGML_MI355X_FIN")) != 0;
+    static const bool fin_env = env_on("GGML_MI355X_FIN");
     if (fin_env && nc == 1 && grp[0].epi == EPI_GLU && !grp[0].eid && c->fin_img && !mul_mat_vec_q_stream_takes(grp, nc, K, in, rope)) {
         const int jn = next_real(g, last);
         const struct ggml_tensor * gl = g->nodes[last];
@@ -568,19 +579,18 @@ static int try_fused_mmv(mi_backend_ctx * c, struct ggml_cgraph * g, int i, int 
             c->pass.pp.active = false;
         }
     }
-    emit_mmv(c, grp, nc, K, in, rope, fin_t ? &fin : nullptr);
+    emit_mmv(c, grp, nc, K, in, rope, fin_t ? &fin : nullptr, wbytes);
     if (fin_t) {
         c->pass.aq = { fin_t->data, grp[0].m, 1, 1, fin_t->nb[1], 0, fin.kind, fin_q, true, (size_t) grp[0].m*4, 0, from, last };
     }
-    c->cnt.mmvq_launches++; c->cnt.weight_bytes += wbytes;
-    for (int r = 0; r < n_def; r++) compute_node(c, g, deferred[r]);       // (flushes a held-back launch first)
+    for (int r = 0; r < n_def; r++) compute_node(c, g, deferred[r]);
     return last;
 }
 
 // the quantized many-token mat-mul that is the ONLY reader of t and directly follows node `last`, or NULL: its producer may then emit the
 // bf16 activation copy itself (and skip the f32 tensor)
 static const struct ggml_tensor * prefill_mm_consumer(mi_backend_ctx * c, const struct ggml_cgraph * g, int last, const struct ggml_tensor * t) {
-    static const bool on = !getenv("GGML_MI355X_PREFILL_BF16_OUT") || atoi(getenv("GGML_MI355X_PREFILL_BF16_OUT")) != 0;
+    static const bool on = env_on("GGML_MI355X_PREFILL_BF16_OUT");
     const int j = next_real(g, last);
     if (!on || j < 0 || j == g->n_nodes - 1) return nullptr;      // (a view that ends at the consumer: the eval-callback case — its src1 must exist as f32)
     const struct ggml_tensor * n = g->nodes[j];
@@ -733,7 +743,7 @@ static int try_fused_moe_combine(mi_backend_ctx * c, struct ggml_cgraph * g, int
     if (!ggml_is_contiguous(out) || ((uintptr_t) out->data % 16)) return 0;
     // the sum's first reader is the norm of a grouped mat-vec launch (the next layer's norm + QKV, or the final norm + lm_head): that launch's prologue
     // evaluates the combine itself (weighted planes, mmvq_stream.h) — this kernel and its boundary go. Anything else: pp_flush runs it after all.
-    static const bool defer_on = !getenv("GGML_MI355X_MOE_COMBINE_DEFER") || atoi(getenv("GGML_MI355X_MOE_COMBINE_DEFER")) != 0;
+    static const bool defer_on = env_on("GGML_MI355X_MOE_COMBINE_DEFER");
     // the values this combine gathers are the ones the router just ranked (same tensors): its top-8 list is probs[ids[u]] already
     const bool direct = c->pass.rt.valid && c->moe_ws && pr->data == c->pass.rt.vals && ids->data == c->pass.rt.sorted && ids->nb[0] == 4;
     if (direct) c->cnt.moe_combine_direct++;
@@ -827,9 +837,7 @@ static int try_fused_moe_experts(mi_backend_ctx * c, struct ggml_cgraph * g, int
                                bg ? (const float *) bg->src[1]->data : nullptr, bu ? (const float *) bu->src[1]->data : nullptr,
                                oai ? op_f32(gl, 2) : 0.0f, oai ? op_f32(gl, 3) : 0.0f };
                 }
-                mul_mat_vec_q_fused(grp, n_used, K, in, nullptr, c->stream);
-                c->cnt.mmvq_launches++; c->cnt.kernels_launched++;
-                c->cnt.weight_bytes += (uint64_t) 2*n_used*M*ggml_row_size(as->type, K);
+                emit_mmv(c, grp, n_used, K, in, nullptr, nullptr, (uint64_t) 2*n_used*M*ggml_row_size(as->type, K));
                 return jg - i + 1;
             }
         }
@@ -851,9 +859,7 @@ static int try_fused_moe_experts(mi_backend_ctx * c, struct ggml_cgraph * g, int
                    bias ? (const float *) bias->data : nullptr, nullptr, nullptr, 0, 0, (const int32_t *) ids->data + u, as->nb[2], b->ne[1] > 1 ? (int)((size_t) u*b->nb[1]/4) : 0 };
         grp[u].res_eid = bias ? 1 : 0;
     }
-    mul_mat_vec_q_fused(grp, n_used, K, in, nullptr, c->stream);
-    c->cnt.mmvq_launches++; c->cnt.kernels_launched++;
-    c->cnt.weight_bytes += (uint64_t) n_used*M*ggml_row_size(as->type, K);
+    emit_mmv(c, grp, n_used, K, in, nullptr, nullptr, (uint64_t) n_used*M*ggml_row_size(as->type, K));
     return consumed;
 }
 
@@ -917,7 +923,7 @@ static bool moe_mmq_ok(const struct ggml_tensor * n) {
     return n->type == GGML_TYPE_F32 && n->nb[0] == 4 && n->ne[0] == as->ne[1] && n->ne[1] == n_used && n->ne[2] == n_tokens && n->ne[3] == 1;
 }
 static int try_fused_prefill_moe(mi_backend_ctx * c, struct ggml_cgraph * g, int i) {
-    static const bool on = !getenv("GGML_MI355X_PREFILL_MOE") || atoi(getenv("GGML_MI355X_PREFILL_MOE")) != 0;
+    static const bool on = env_on("GGML_MI355X_PREFILL_MOE");
     if (!on) return 0;
     struct ggml_tensor * up = g->nodes[i];
     if (!moe_mmq_ok(up) || up->src[1]->ne[1] != 1 || !is_internal(c, up)) return 0;
@@ -1000,7 +1006,7 @@ static int try_fused_prefill_moe(mi_backend_ctx * c, struct ggml_cgraph * g, int
     // (pp512 18.7k -> 22.2k tok/s). Many (Mixtral: ~128): the dual kernel's single workgroup per CU decodes at half the rate of two 128-pair workgroups (926 us against
     // 2 x 350 - 390 + 62 for the GLU kernel), so the two products stay separate launches of the 128-pair kernel: the up launch writes its tensor, the gate launch reads
     // it back in its epilogue and evaluates the GLU there.
-    static const int dual_env = getenv("GGML_MI355X_MOE_DUAL") ? atoi(getenv("GGML_MI355X_MOE_DUAL")) : -1;
+    static const int dual_env = (int) env_int("GGML_MI355X_MOE_DUAL", -1);
     const int dual_opt = c->moe_dual >= 0 ? c->moe_dual : dual_env;
     const bool dual = dual_opt >= 0 ? dual_opt != 0 : n_used*n_tokens <= 96*E;
     const int tile = dual ? 256 : mul_mat_q_id_tile(n_used, n_tokens, E);
@@ -1080,7 +1086,7 @@ static int try_fused_moe_route(mi_backend_ctx * c, struct ggml_cgraph * g, int i
     }
     if (nd->op != GGML_OP_ARGSORT || nd->src[0] != cur || nd->op_params[0] != GGML_SORT_ORDER_DESC || nd->type != GGML_TYPE_I32 ||
         !ggml_is_contiguous(nd) || ggml_nelements(nd) != E) return 0;
-    static const bool topv_on = !getenv("GGML_MI355X_MOE_TOPV") || atoi(getenv("GGML_MI355X_MOE_TOPV")) != 0;
+    static const bool topv_on = env_on("GGML_MI355X_MOE_TOPV");
     float * topv = topv_on && c->moe_ws ? c->moe_ws + 64 : nullptr;
     if (norm) {
         if (!moe_route_norm_supported(K, E, c->moe_ws) || ((uintptr_t) normw->data % 16) || ((uintptr_t) norm->src[0]->data % 16) || ((uintptr_t) x->data % 16)) return 0;
@@ -1098,7 +1104,7 @@ static int try_fused_moe_route(mi_backend_ctx * c, struct ggml_cgraph * g, int i
 // Prefill: MUL_MAT(gate) ; MUL_MAT(up) -> GLU(swiglu) on the same many-token activations (build_ffn, src/llama-graph.cpp:646-691) as one
 // matrix-core kernel (mmq.hip DUAL): neither product is written, the GLU kernel is gone and the activation tile is staged once.
 static int try_fused_prefill_glu(mi_backend_ctx * c, struct ggml_cgraph * g, int i) {
-    static const bool on = !getenv("GGML_MI355X_PREFILL_GLU") || atoi(getenv("GGML_MI355X_PREFILL_GLU")) != 0;
+    static const bool on = env_on("GGML_MI355X_PREFILL_GLU");
     if (!on) return 0;
     struct ggml_tensor * n = g->nodes[i];
     const struct ggml_tensor * a = n->src[0]; const struct ggml_tensor * b = n->src[1];
@@ -1138,7 +1144,7 @@ static int try_fused_prefill_glu(mi_backend_ctx * c, struct ggml_cgraph * g, int
 // (1024 rows) are 32 tiles on 256 CUs. The ROPEs run after the launch, i.e. later than in graph order relative to the following
 // mat-muls: allowed only if no output of one chain overlaps an output of another (the allocator may have recycled a dead buffer).
 static int try_fused_prefill_qkv(mi_backend_ctx * c, struct ggml_cgraph * g, int i) {
-    static const bool on = !getenv("GGML_MI355X_PREFILL_QKV") || atoi(getenv("GGML_MI355X_PREFILL_QKV")) != 0;
+    static const bool on = env_on("GGML_MI355X_PREFILL_QKV");
     if (!on) return 0;
     const struct ggml_tensor * b = g->nodes[i]->src[1];
     // a chain: MUL_MAT [-> ADD bias (gpt-oss's bq / bk / bv, src/llama-model.cpp:17636-17645)] [-> (RESHAPE ->) ROPE]; the ADDs run as their own launches behind the
@@ -1283,7 +1289,7 @@ static int try_fused_prefill_add(mi_backend_ctx * c, struct ggml_cgraph * g, int
     if (other == n || other->type != GGML_TYPE_F32 || (!ggml_are_same_shape(other, n) && !bias_row) || other->nb[0] != 4) return 0;
     // the sum is the residual stream; if RMS_NORM -> MUL(w) reads it next (ffn_norm, the next layer's attn_norm: build_norm, src/llama-graph.cpp:597-630)
     // and the mat-mul splits k, ONE pass adds the planes and the residual, writes the sum and normalises it
-    static const bool norm_on = !getenv("GGML_MI355X_PREFILL_COMBINE_NORM") || atoi(getenv("GGML_MI355X_PREFILL_COMBINE_NORM")) != 0;
+    static const bool norm_on = env_on("GGML_MI355X_PREFILL_COMBINE_NORM");
     struct ggml_tensor * nrm = nullptr; struct ggml_tensor * mul = nullptr; const struct ggml_tensor * w = nullptr;
     const int jn = next_real(g, j);
     if (norm_on && !bias_row && jn > 0 && jn + 1 < g->n_nodes && g->nodes[jn]->op == GGML_OP_RMS_NORM && g->nodes[jn]->src[0] == nx && g->nodes[jn + 1]->op == GGML_OP_MUL) {

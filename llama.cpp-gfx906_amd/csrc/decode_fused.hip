@@ -404,7 +404,7 @@ __global__ void __launch_bounds__(HD) k_attn_merge(const attn_args p) {
 bool attn_decode_supported(int64_t head_dim, int64_t n_kv) { return (head_dim == 128 || head_dim == 64) && n_kv % 8 == 0 && n_kv*4 <= 48*1024; }
 // measured (tg1024 / --fa 1 tg128): the transposed-V kernel gains from 384-512 cells on, the row-V (flash attention) one already at 256
 static int64_t attn_split_min(bool v_trans = true) {
-    static const int64_t v = getenv("GGML_MI355X_ATTN_SPLIT_MIN") ? atoll(getenv("GGML_MI355X_ATTN_SPLIT_MIN")) : 0;
+    static const int64_t v = env_int("GGML_MI355X_ATTN_SPLIT_MIN", 0);
     return v ? (v < 256 ? 256 : v) : (v_trans ? 384 : 256);
 }
 bool attn_decode_supported_split(int64_t head_dim, int64_t n_kv) { return (head_dim == 128 || head_dim == 64) && n_kv >= attn_split_min(true) && n_kv % 32 == 0; }
@@ -442,11 +442,11 @@ void attn_decode(const void * q, size_t q_nb1, size_t q_nb2, const void * k, siz
     if (v_trans ? !((kt == T_F16 || kt == T_Q8_0) && vy == T_F16) : !attn_decode_kv_types_fused(kt, vy)) { fprintf(stderr, "attn_decode: KV types (%d, %d) have no kernel\n", kt, vy); abort(); }
     // long contexts: one workgroup per (head, token) walks every cell alone — 32 workgroups on 256 CUs. With a partial buffer the cells
     // are split into ranges of >= 256 (at most 32 ranges) that run side by side and a small second kernel merges them.
-    static const bool split_on = !getenv("GGML_MI355X_ATTN_SPLIT") || atoi(getenv("GGML_MI355X_ATTN_SPLIT")) != 0;
+    static const bool split_on = env_on("GGML_MI355X_ATTN_SPLIT");
     const size_t need = attn_decode_part_bytes(head_dim, n_kv, n_head, T);
     // row-major V (flash attention) at exactly the padding size: most cells of a short context are masked padding — one workgroup per head that stops at the last
     // live cell beats two ranges + a merge launch there (GGML_MI355X_ATTN_LIVE_SCAN=0: the split as before)
-    static const bool live_on = !getenv("GGML_MI355X_ATTN_LIVE_SCAN") || atoi(getenv("GGML_MI355X_ATTN_LIVE_SCAN")) != 0;
+    static const bool live_on = env_on("GGML_MI355X_ATTN_LIVE_SCAN");
     const bool live_scan = live_on && !v_trans && mask && n_kv == 256 && T == 1;
     a.live_scan = live_scan ? 1 : 0;
     if (!live_scan && part && need && need <= part_bytes && n_kv >= attn_split_min(v_trans) && (split_on || n_kv*4 > 48*1024)) {

@@ -796,16 +796,15 @@ __global__ void __launch_bounds__(256) k_moe_route_wide(const moe_route_args p, 
         if (p.topv && rank < 8) p.topv[rank] = me;
     }
 }
+static bool moe_route_wide_on() { static const bool on = env_on("GGML_MI355X_MOE_ROUTE_WIDE"); return on; }
 bool moe_route_norm_supported(int64_t k, int64_t n_expert, const float * ws) {
-    static const bool wide_on = !getenv("GGML_MI355X_MOE_ROUTE_WIDE") || atoi(getenv("GGML_MI355X_MOE_ROUTE_WIDE")) != 0;
-    return ws && wide_on && n_expert >= 4 && n_expert <= 256 && k % 4 == 0;
+    return ws && moe_route_wide_on() && n_expert >= 4 && n_expert <= 256 && k % 4 == 0;
 }
 void moe_route(const float * w, size_t w_nb1, const float * x, const float * bias, int64_t k, int64_t n_expert, bool softmax,
                float * logits, float * probs, int32_t * sorted, hipStream_t stream, float * ws, const float * norm_w, float eps, float * y_out, unsigned * err, float * topv) {
     moe_route_args a = { w, w_nb1, x, bias, (int) k, (int) n_expert, softmax ? 1 : 0, logits, probs, sorted, norm_w, eps, y_out, err, topv };
-    static const bool wide_on = !getenv("GGML_MI355X_MOE_ROUTE_WIDE") || atoi(getenv("GGML_MI355X_MOE_ROUTE_WIDE")) != 0;
     if (norm_w && !moe_route_norm_supported(k, n_expert, ws)) { fprintf(stderr, "moe_route: the norm is folded into the multi-workgroup kernel only\n"); abort(); }
-    if (ws && wide_on && n_expert >= 4 && n_expert <= 256) hipLaunchKernelGGL(k_moe_route_wide, dim3((unsigned)((n_expert + MR_EPW - 1)/MR_EPW)), dim3(256), 0, stream, a, ws);
+    if (ws && moe_route_wide_on() && n_expert >= 4 && n_expert <= 256) hipLaunchKernelGGL(k_moe_route_wide, dim3((unsigned)((n_expert + MR_EPW - 1)/MR_EPW)), dim3(256), 0, stream, a, ws);
     else hipLaunchKernelGGL(k_moe_route, dim3(1), dim3(1024), 0, stream, a);
 }
 
@@ -910,8 +909,7 @@ __global__ void __launch_bounds__(512) k_hbm_read_q4k(const char * p, int n_pair
     if (acc == 0x12345678) *sink = acc;
 }
 void hbm_read_probe(const void * p, size_t bytes, unsigned * sink, hipStream_t stream) {
-    static int mode = -1;
-    if (mode < 0) { const char * e = getenv("GGML_MI355X_PROBE_MODE"); mode = e ? atoi(e) : 0; }
+    static const int mode = (int) env_int("GGML_MI355X_PROBE_MODE", 0);
     if (mode == 1) hipLaunchKernelGGL(k_hbm_read_q4k, dim3(256), dim3(512), 0, stream, (const char *) p, (int)(bytes/4608), sink);
     else           hipLaunchKernelGGL(k_hbm_read, dim3(256*8), dim3(256), 0, stream, (const int4v *) p, bytes/16, sink);
 }

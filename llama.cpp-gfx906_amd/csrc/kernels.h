@@ -2,11 +2,16 @@
 // strides in BYTES (ggml nb[] convention) and a hipStream_t; no ggml types, so the
 // kernels can be driven from backend*.cpp (ggml tensors) or from the flat C-ABI in
 // include/ggml-mi355x.h. Every launcher is asynchronous on `stream` and performs
-// no allocation or synchronisation (safe under hipGraph capture).
+// no allocation or synchronisation (safe under hipGraph capture). A launcher has put
+// all its kernels on the stream when it returns and keeps nothing from one call to
+// the next: what a caller wants back (a kernel's name, its timing) goes through the
+// call's arguments. Run-time switches are read through env_switch.h.
 #pragma once
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include "env_switch.h"
 
 namespace mi355x {
 
@@ -273,25 +278,20 @@ bool mul_mat_vec_q_fused_supported(int64_t k, int act_kind);
 bool mul_mat_vec_q_fused_prologue_supported(int64_t k, int act_kind);        // PRO_QUANT / PRO_NORM limits (k % 256, or k % 32 with Q8_0 activations)
 bool mul_mat_vec_q_fused_can_group(int type_a, int type_b);         // may these two weight types share one grouped launch
 bool mul_mat_vec_q_fused_can_group_mixed(int type_a, int type_b);   // pairs of different activation formats (only when the launch quantizes the activation itself)
+// the optional timing record of ONE grouped launch, filled per call (NULL: not profiling; the module keeps no launch state of its own). e0 != NULL: the
+// launch carries (e0, e1) as its dispatch's start / stop events (hipExtLaunchKernelGGL). kernel: the launcher stores the name of the instantiation it used,
+// spelled as rocprofv3's kernel trace spells it
+struct mmvq_launch_rec { hipEvent_t e0, e1; const char * kernel; };
+// every kernel of the launch is on `stream` when this returns
 void mul_mat_vec_q_fused(const mmvq_group * groups, int n_groups, int64_t k, const mmvq_input & in, const mmvq_rope * rope, hipStream_t stream,
-                         const mmvq_fin * fin = nullptr);
+                         const mmvq_fin * fin = nullptr, mmvq_launch_rec * rec = nullptr);
 // the streamed form of the grouped launch (mmvq_stream.h: loader wave + LDS slot ring + one 256-weight unit per lane): K-quant weights in
 // contiguous rows, no expert stacks; mul_mat_vec_q_fused routes to it when mul_mat_vec_q_stream_takes says so (it never writes an mmvq_fin image)
 bool mul_mat_vec_q_stream_enabled(void);       // GGML_MI355X_STREAM (default 1)
 bool mul_mat_vec_q_stream_takes(const mmvq_group * groups, int n_groups, int64_t k, const mmvq_input & in, const mmvq_rope * rope);
 void mul_mat_vec_q_stream(const mmvq_group * groups, int n_groups, int64_t k, const mmvq_input & in, const mmvq_rope * rope, hipStream_t stream,
-                          hipEvent_t e0, hipEvent_t e1, const char ** kernel_name);
+                          mmvq_launch_rec * rec = nullptr);
 bool mul_mat_vec_q_fused_fin_supported(int64_t m, int64_t k_in);   // may a GLU launch with m output rows carry an mmvq_fin
-int  mul_mat_vec_q_fused_share(const mmvq_group * groups, int n_groups, int fw, int * block_end);   // workgroups per group (one workgroup per CU in all)
-// (round 1's chained launch held launches back; nothing is held back any more: flush is a no-op kept for its call sites)
-void mul_mat_vec_q_fused_flush(hipStream_t stream);
-// called right before / after every kernel this module puts on the stream (type of the first group, weight bytes, launches merged, k)
-typedef void (*mmvq_launch_hook)(void * ctx, int type, uint64_t weight_bytes, int n_merged, int64_t k);
-// the NEXT grouped launch carries (e0, e1) as its dispatch's start / stop events (hipExtLaunchKernelGGL); consumed by that launch
-void mul_mat_vec_q_fused_set_launch_events(hipEvent_t e0, hipEvent_t e1);
-const char * mul_mat_vec_q_fused_last_kernel(void);     // name of the instantiation the last grouped launch used
-void mul_mat_vec_q_fused_set_hooks(mmvq_launch_hook pre, mmvq_launch_hook post, void * ctx);
-int  mul_mat_vec_q_fused_pending(uint64_t * weight_bytes);
 
 // ---- small uploads batched into one launch (backend.cpp: be_set_tensor_async / uploads_flush) ----
 constexpr int UPLOAD_BATCH_MAX = 12;

@@ -991,7 +991,8 @@ __global__ void __launch_bounds__(768) __attribute__((amdgpu_waves_per_eu(3, 3))
     }
 }
 constexpr size_t MQ_LDS_BYTES_WS256 = 2*((size_t) 256*MQ_LD + MQ_WS_XTILE);
-static bool mmq_ws_on() { static const bool on = !getenv("GGML_MI355X_MMQ_WS") || atoi(getenv("GGML_MI355X_MMQ_WS")) != 0; return on; }
+static bool mmq_ws_on() { static const bool on = env_on("GGML_MI355X_MMQ_WS"); return on; }
+static bool mmq_w16_on() { static const bool on = env_on("GGML_MI355X_MMQ16"); return on; }
 
 constexpr size_t MQ_LDS_BYTES = 4*(size_t) MQ_BM*MQ_LD;
 constexpr size_t MQ_LDS_BYTES_256 = 2*(size_t)(MQ_BM + 256)*MQ_LD;
@@ -1001,7 +1002,7 @@ constexpr size_t MQ_LDS_BYTES_DUAL = 2*(size_t)(2*MQ_BM + 256)*MQ_LD;
 template <int T_>
 static void launch_mmq_wide(dim3 grid, const mmq_args & a, hipStream_t stream) {
     MI_LDS_LIMIT_OR_DIE(MQ_LDS_BYTES_256, k_mmq<T_, 256>);
-    static const bool w16 = !getenv("GGML_MI355X_MMQ16") || atoi(getenv("GGML_MI355X_MMQ16")) != 0;
+    const bool w16 = mmq_w16_on();
     if (w16 && !a.moe && a.ne12 == 1 && a.r2 == 1 && a.r3 == 1) {
         MI_LDS_LIMIT_OR_DIE(MQ_LDS_BYTES_256, k_mmq16<T_>);
         hipLaunchKernelGGL((k_mmq16<T_>), grid, dim3(1024), MQ_LDS_BYTES_256, stream, a);
@@ -1048,7 +1049,7 @@ void mul_mat_q(int type_a, const void * W, size_t w_row_stride, int64_t m, int64
     const bool vec_ok = m % 4 == 0 && dst_col_stride_bytes % 16 == 0 && ((uintptr_t) dst % 16) == 0 && (!res || (res_row_stride % 16 == 0 && ((uintptr_t) res % 16) == 0));
     // few rows (wo: m = 4096, k = 4096; ffn_down: k = 14336): 256-token tiles and k in four parts (with the 16-wave kernel this beats
     // 128-token tiles split in two also at k = 4096: wo 49 -> 42 us)
-    static const int64_t wide4_min_k = getenv("GGML_MI355X_WIDE4_MINK") ? atoll(getenv("GGML_MI355X_WIDE4_MINK")) : 4096;
+    static const int64_t wide4_min_k = env_int("GGML_MI355X_WIDE4_MINK", 4096);
     const bool wide4 = n >= 256 && wtiles < 160 && wtiles*4 >= 160 && k % 1024 == 0 && k >= wide4_min_k && vec_ok;
     const bool wide = (n >= 256 && wtiles >= 160) || wide4;
     const int ntiles = wide ? (int)((n + 255)/256) : (int)((n + MQ_BN - 1)/MQ_BN);
@@ -1109,7 +1110,7 @@ __global__ void __launch_bounds__(256) k_combine_seg(const combine_seg_args p) {
 template <int T_, int T2_>
 static void launch_mmq_multi(dim3 grid, const mmq_args & a, hipStream_t stream) {
     MI_LDS_LIMIT_OR_DIE(MQ_LDS_BYTES_256, k_mmq<T_, 256, false, T2_>);
-    static const bool w16 = !getenv("GGML_MI355X_MMQ16") || atoi(getenv("GGML_MI355X_MMQ16")) != 0;
+    const bool w16 = mmq_w16_on();
     if (w16) {
         MI_LDS_LIMIT_OR_DIE(MQ_LDS_BYTES_256, k_mmq16<T_, T2_>);
         hipLaunchKernelGGL((k_mmq16<T_, T2_>), grid, dim3(1024), MQ_LDS_BYTES_256, stream, a);
@@ -1123,7 +1124,7 @@ bool mul_mat_q_multi(int nseg, const int * types, const void * const * W, const 
                      int64_t k, const float * x, size_t x_row_stride, int64_t n, void * scratch, size_t scratch_size, bool scratch_ready,
                      const mmvq_rope * rope, const int * seg_rope, const mmq_kv_store * kvs, hipStream_t stream, const float * const * seg_bias) {
     if (nseg < 2 || nseg > 3 || n < 256) return false;
-    static const bool w16 = !getenv("GGML_MI355X_MMQ16") || atoi(getenv("GGML_MI355X_MMQ16")) != 0;
+    const bool w16 = mmq_w16_on();
     if (rope) {        // epilogue / combine-pass ROPE: 16-wave kernel only, heads of an even size that start at column multiples of 4
         if (!w16 || rope->head_dim % 4 != 0 || rope->p.n_dims % 2 != 0) return false;
         for (int s = 0; s < nseg; s++) if (seg_rope[s] && m[s] % rope->head_dim != 0) return false;
@@ -1213,7 +1214,7 @@ void mul_mat_q_glu(int type_a, const void * Wg, const void * Wu, size_t w_row_st
     }
     mmq_args a = { (const char *) Wg, w_row_stride, 0, 0, (int) m, (int) k, xb, (int) n, (char *) dst, dst_col_stride_bytes, 0, 0, 1, 1, 1, 1, 0, nullptr, nullptr, 0, y16, (const char *) Wu, nullptr, 0, 0, 0 };
     a.mtiles = (int)((m + MQ_BM - 1)/MQ_BM);
-    { static const int dbg = getenv("GGML_MI355X_MMQ_DBG") ? atoi(getenv("GGML_MI355X_MMQ_DBG")) : 0; a.dbg = dbg; }
+    { static const int dbg = (int) env_int("GGML_MI355X_MMQ_DBG", 0); a.dbg = dbg; }
     const dim3 grid((unsigned)((n + 255)/256), (unsigned) a.mtiles, 1);
     switch (type_a) {
         case T_Q4_0:  launch_mmq_dual<T_Q4_0>(grid, a, stream);  break;
@@ -1275,7 +1276,7 @@ mmq_moe_plan mul_mat_q_id_plan(void * scratch, int64_t k, int64_t n_tokens, int6
     return pl;
 }
 int mul_mat_q_id_tile(int64_t n_used, int64_t n_tokens, int64_t n_expert) {
-    static const int forced = getenv("GGML_MI355X_MOE_TILE") ? atoi(getenv("GGML_MI355X_MOE_TILE")) : 0;
+    static const int forced = (int) env_int("GGML_MI355X_MOE_TILE", 0);
     if (forced == 128 || forced == 256) return forced;
     // measured at 512 tokens: Mixtral (~128 pairs per expert, every wave of a tile multiplies): 128-pair tiles 9.85k tok/s, 256-pair tiles on the 16-wave kernel 7.9k
     // (on k_mmq<256> 6.97k); gpt-oss (64 pairs per expert: a quarter of the 16-wave kernel's waves multiply, all sixteen decode): 256-pair tiles 22.85k, 128-pair 21.7k

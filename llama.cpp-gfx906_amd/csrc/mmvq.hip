@@ -263,8 +263,7 @@ static void launch_mmvq_n(const mmvq_args & a, int act_kind, int64_t n_pairs, hi
     // 27.4) but not for the K-quants, whose n dot chains per block are VALU-bound either way (Q4_K n = 8: 29.5 -> 35.5 us with 2 waves
     // per SIMD; 16 waves per workgroup spill) — those keep the simple kernel until the int8 MFMA kernel exists
     if (NCOLS > 1 && !IDS && a.n_batch <= 1 && (TYPE == T_Q8_0 || TYPE == T_Q4_0)) {
-        static int use_cols = -1;
-        if (use_cols < 0) { const char * e = getenv("GGML_MI355X_MMVQ_COLS"); use_cols = e ? atoi(e) : 1; }
+        static const int use_cols = (int) env_int("GGML_MI355X_MMVQ_COLS", 1);
         if (use_cols && launch_mmvq_cols<TYPE, (NCOLS > 1 ? NCOLS : 2)>(a, act_kind, stream)) return;
     }
     hipLaunchKernelGGL((k_mmvq<TYPE, NCOLS, R, false, IDS>), grid, dim3(256), 0, stream, a);

@@ -319,8 +319,7 @@ static bool launch_cols_mfma(colmf_args & a, size_t lds, hipStream_t stream) {
 // false = not taken (format, shape or LDS size): the caller runs its own kernel
 bool mul_mat_vec_q_cols_mfma(int type_a, const void * W, size_t w_row_stride, int64_t m, int64_t k,
                              const act_q8 & act, int64_t n, float * dst, size_t dst_col_stride_bytes, hipStream_t stream) {
-    static int on = -1;
-    if (on < 0) { const char * e = getenv("GGML_MI355X_MMVQ_COLS_MFMA"); on = e ? atoi(e) : 1; }
+    static const int on = (int) env_int("GGML_MI355X_MMVQ_COLS_MFMA", 1);
     if (!on || n < 2 || n > 8 || act.kind != T_Q8_K || k % 256 != 0 || m < 16 || m >= (1ll << 27) || k >= (1ll << 24)) return false;
     if (type_a != T_Q4_K && type_a != T_Q5_K && type_a != T_Q6_K) return false;
     // Where it pays (rocprofv3 kernel times, 4096 x 14336, profiles/r02_*cols*): this kernel costs ~14 us + 0.4 us per column (its 16-row
@@ -340,8 +339,7 @@ bool mul_mat_vec_q_cols_mfma(int type_a, const void * W, size_t w_row_stride, in
     a.a_qs = act.qs; a.a_d = act.d; a.a_bs = act.bsums;
     a.dst = dst; a.dst_col_stride = dst_col_stride_bytes;
     a.n_tiles = (int)((m + 15)/16);
-    static int dbg = -1;
-    if (dbg < 0) { const char * e = getenv("GGML_MI355X_COLS_DBG"); dbg = e ? atoi(e) : 0; }
+    static const int dbg = (int) env_int("GGML_MI355X_COLS_DBG", 0);
     a.dbg = dbg;
     switch (type_a) {
         case T_Q4_K: return launch_cols_mfma<T_Q4_K>(a, lds, stream);

@@ -565,28 +565,27 @@ __global__ void __launch_bounds__(FWT*64, FWT == 8 ? 2 : 1) k_mmvq_fused(const f
     else                            fused_body<TB, GLU, PRO, NA, DB, FWT, EXT>(p, sel, smem, lane, wave);
 }
 
-// Timing hook: when the host set an event pair (option "profile"), the launch carries it as the DISPATCH's own start / stop events
-// (hipExtLaunchKernelGGL): hipEventElapsedTime(ev0, ev1) is then the kernel's execution time by the same packet timestamps rocprofv3's
-// kernel trace reports — not "launch call to completion" as a pair of hipEventRecord around the launch measures
-extern hipEvent_t mi355x_fused_ev0, mi355x_fused_ev1;
-extern const char * mi355x_fused_last_kernel;       // the instantiation the last launch used, spelled as rocprofv3's kernel trace spells it
+// Timing: a launch whose record (fused_launch::rec, the caller's mmvq_launch_rec) holds an event pair carries it as the DISPATCH's own start / stop
+// events (hipExtLaunchKernelGGL): hipEventElapsedTime(e0, e1) is then the kernel's execution time by the same packet timestamps rocprofv3's
+// kernel trace reports — not "launch call to completion" as a pair of hipEventRecord around the launch measures. Every launch with a record
+// stores the name of its instantiation there, spelled as rocprofv3's kernel trace spells it
 template <int TA, int TB, bool GLU, int PRO, int NA, int D, int FWT = 8, bool EXT = false> static const char * fused_kname() {
     static char name[96] = "";
     if (!name[0]) snprintf(name, sizeof(name), "k_mmvq_fused<%d, %d, %s, %d, %d, %d, %d, %s>", TA, TB, GLU ? "true" : "false", PRO, NA, D, FWT, EXT ? "true" : "false");
     return name;
 }
 #define MI_UNP(...) __VA_ARGS__
-// the single-tensor instantiations exist twice: with and without the extended epilogue
+// (both macros launch the fused_launch `L` of their scope) the single-tensor instantiations exist twice: with and without the extended epilogue
 #define MI_FLX(TARGS6_, FW_, grid_, block_, lds_, stream_, a_) do { \
     if (L.ext) MI_FL((MI_UNP TARGS6_, FW_, true), grid_, block_, lds_, stream_, a_); \
     else       MI_FL((MI_UNP TARGS6_, FW_, false), grid_, block_, lds_, stream_, a_); } while (0)
 #define MI_FL(TARGS_, grid_, block_, lds_, stream_, a_) do { \
-    mi355x_fused_last_kernel = fused_kname<MI_UNP TARGS_>(); \
-    if (mi355x_fused_ev0) { hipExtLaunchKernelGGL((k_mmvq_fused<MI_UNP TARGS_>), grid_, block_, lds_, stream_, mi355x_fused_ev0, mi355x_fused_ev1, 0, a_); mi355x_fused_ev0 = nullptr; mi355x_fused_ev1 = nullptr; } \
+    if (L.rec) L.rec->kernel = fused_kname<MI_UNP TARGS_>(); \
+    if (L.rec && L.rec->e0) hipExtLaunchKernelGGL((k_mmvq_fused<MI_UNP TARGS_>), grid_, block_, lds_, stream_, L.rec->e0, L.rec->e1, 0, a_); \
     else hipLaunchKernelGGL((k_mmvq_fused<MI_UNP TARGS_>), grid_, block_, lds_, stream_, a_); } while (0)
 
 // a grouped launch, prepared on the host
-struct fused_launch { fused_mmvq_args a; int blocks; size_t lds; int ta, tb; bool glu; int mode, na; bool deep; int64_t k; uint64_t wbytes; int fw; bool ext; };
+struct fused_launch { fused_mmvq_args a; int blocks; size_t lds; int ta, tb; bool glu; int mode, na; bool deep; int fw; bool ext; mmvq_launch_rec * rec; };
 
 // the launcher of one {TA, TB} kernel family: picks the instantiation for L's prologue / activation size class / ring depth
 #define MI_DEFINE_FUSED_LAUNCHER(NAME_, TA_, TB_, HAS_GLU_) \

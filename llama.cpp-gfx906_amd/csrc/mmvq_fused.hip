@@ -1,5 +1,7 @@
-// mmvq_fused.hip — host side of the persistent grouped mat-vec (device code: mmvq_fused.h, kernels: mmvq_fused_<type>.hip):
-// shares the workgroups among the groups, fills the argument block, picks the kernel family.
+// mmvq_fused.hip — host side of the persistent grouped mat-vec (device code: mmvq_fused.h, kernels: mmvq_fused_<type>.hip): routes a launch to the
+// streamed kernels (mmvq_stream.hip) or the register-ring kernels here; for the latter shares the workgroups among the groups, fills the argument
+// block, picks the kernel family. Every launch is issued inside the call; what a caller wants timed or named travels in the call's mmvq_launch_rec.
+// No mutable state outside the -DMI_STAMPS diagnostic build.
 #include "mmvq_fused.h"
 
 #include <limits.h>
@@ -45,15 +47,6 @@ bool mul_mat_vec_q_fused_supported(int64_t k, int act_kind) {
 }
 bool mul_mat_vec_q_fused_prologue_supported(int64_t k, int act_kind) { return (k % 256 == 0 || (act_kind == T_Q8_0 && k % 32 == 0)) && k <= 16*1024; }
 
-// per host thread: one backend (stream) is driven by one thread at a time, different backends concurrently from different threads
-// (tests/test-thread-safety.cpp)
-static thread_local struct { mmvq_launch_hook pre = nullptr, post = nullptr; void * ctx = nullptr; } g_hook;
-hipEvent_t mi355x_fused_ev0 = nullptr, mi355x_fused_ev1 = nullptr;
-const char * mi355x_fused_last_kernel = "";
-const char * mul_mat_vec_q_fused_last_kernel(void) { return mi355x_fused_last_kernel; }
-void mul_mat_vec_q_fused_set_launch_events(hipEvent_t e0, hipEvent_t e1) { mi355x_fused_ev0 = e0; mi355x_fused_ev1 = e1; }
-void mul_mat_vec_q_fused_set_hooks(mmvq_launch_hook pre, mmvq_launch_hook post, void * ctx) { g_hook.pre = pre; g_hook.post = post; g_hook.ctx = ctx; }
-
 static int device_cu_count() {
     static int n_cu = 0;
     if (n_cu == 0) {
@@ -93,9 +86,6 @@ static int share_groups(const mmvq_group * groups, int n_groups, int fw, int bud
     }
     return blocks;
 }
-int mul_mat_vec_q_fused_share(const mmvq_group * groups, int n_groups, int fw, int * block_end) {
-    return share_groups(groups, n_groups, fw, device_cu_count(), block_end);
-}
 
 // ---- the rotation table of one token: tab[2*ip] = cos(theta_ip)*mscale, tab[2*ip + 1] = sin(theta_ip)*mscale, ip < n_dims/2, for the position
 //      pos[0] — elem.hip's k_rope / rope_pair formulas (YaRN ramp, frequency factors), one lane per pair index ----
@@ -132,18 +122,13 @@ static fused_launch fused_prepare(const mmvq_group * groups, int n_groups, int64
     if (fin && fin->kind && n_groups == 1 && groups[0].epi == EPI_GLU && !groups[0].eid && mul_mat_vec_q_fused_fin_supported(groups[0].m, k)) a.fin = *fin;
     a.n_groups = n_groups; a.k = (int) k; a.act_kind = in.act_kind;
     // share the persistent workgroups among the groups in proportion to their rows (never more than one row pair per wave)
-    static int wpc = 0, glu_wpc = 1;   // measured (tools/stamp_timeline.py): the second workgroup on a CU runs its prologue ~2x slower
+    // workgroups per CU: 1, measured (tools/stamp_timeline.py): the second workgroup on a CU runs its prologue ~2x slower
+    static const int wpc = std::max(1, (int) env_int("GGML_MI355X_MMVQ_WPC", 1)), glu_wpc = std::max(1, (int) env_int("GGML_MI355X_GLU_WPC", 1));
     const int n_cu = device_cu_count();
-    if (wpc == 0) {
-        wpc = 1;
-        if (const char * e = getenv("GGML_MI355X_MMVQ_WPC")) wpc = atoi(e) > 0 ? atoi(e) : 1;
-        if (const char * e = getenv("GGML_MI355X_GLU_WPC")) glu_wpc = atoi(e) > 0 ? atoi(e) : 1;
-    }
     int64_t rows_total = 0;
     for (int i = 0; i < n_groups; i++) rows_total += (int64_t) groups[i].m*(groups[i].epi == EPI_GLU ? 2 : 1);
     // 16 waves per workgroup: more than one row pair per wave at 8 waves x CUs, at most one at 16 (the in-prologue-norm launches only)
-    static int fw16_env = -1;
-    if (fw16_env < 0) { const char * e = getenv("GGML_MI355X_MMVQ_FW16"); fw16_env = e ? atoi(e) : 1; }
+    static const bool fw16_env = env_on("GGML_MI355X_MMVQ_FW16");
     const int FW = (fw16_env && groups[0].epi != EPI_GLU && in.mode == PRO_NORM && k <= 4096 && k % 256 == 0 &&
                     (rows_total + 1)/2 > (int64_t) n_cu*8 &&
                     ((rows_total + 1)/2 <= (int64_t) n_cu*16 + 64 || (rows_total + 1)/2 >= (int64_t) n_cu*64)) ? 16 : 8;   // or a long stream (lm_head: 101 -> 96 us)
@@ -218,8 +203,7 @@ static fused_launch fused_prepare(const mmvq_group * groups, int n_groups, int64
     // stream) everywhere 482-486 — a CU's request queue is finite and a wave that cannot queue a load cannot run its share of the
     // prologue either. Only long single-tensor streams (>= 16 steps per wave: the lm_head, 31 row pairs per wave) take the deep ring;
     // GGML_MI355X_MMVQ_DEPTH=2|4 forces one for experiments (the GLU kernels exist with D = 4 only).
-    static int depth_env = -1;
-    if (depth_env < 0) { const char * e = getenv("GGML_MI355X_MMVQ_DEPTH"); depth_env = e ? atoi(e) : 0; }
+    static const int depth_env = (int) env_int("GGML_MI355X_MMVQ_DEPTH", 0);
     int64_t max_steps = 0;
     for (int i = 0; i < n_groups; i++) {
         const int nwg_i = a.block_end[i] - (i ? a.block_end[i - 1] : 0);
@@ -233,8 +217,7 @@ static fused_launch fused_prepare(const mmvq_group * groups, int n_groups, int64
     L.ext = false;      // does any group need the extended epilogue
     for (int i = 0; i < n_groups; i++)
         if ((groups[i].epi == EPI_ROPE && (groups[i].res || (rope && (rope->p.mode & 2)))) || groups[i].res2 || groups[i].res_eid) L.ext = true;
-    L.blocks = blocks; L.lds = lds; L.ta = ta; L.tb = tb; L.glu = glu; L.mode = mode; L.na = na; L.deep = deep; L.k = k;
-    for (int i = 0; i < n_groups; i++) L.wbytes += (uint64_t) groups[i].m*groups[i].row_stride*(groups[i].epi == EPI_GLU ? 2 : 1);
+    L.blocks = blocks; L.lds = lds; L.ta = ta; L.tb = tb; L.glu = glu; L.mode = mode; L.na = na; L.deep = deep;
     return L;
 }
 
@@ -260,36 +243,20 @@ static void fused_launch_kernel(const fused_launch & L, hipStream_t stream) {
     abort();
 }
 
-int mul_mat_vec_q_fused_pending(uint64_t * wbytes) { if (wbytes) *wbytes = 0; return 0; }     // nothing is ever held back (the round-1 chained launch is gone)
-void mul_mat_vec_q_fused_flush(hipStream_t) { }
-
 void mul_mat_vec_q_fused(const mmvq_group * groups, int n_groups, int64_t k, const mmvq_input & in_, const mmvq_rope * rope, hipStream_t stream,
-                         const mmvq_fin * fin) {
+                         const mmvq_fin * fin, mmvq_launch_rec * rec) {
     mmvq_input in = in_;
-    if (in.planes && !mul_mat_vec_q_stream_takes(groups, n_groups, k, in, rope)) {
+    bool streamed = mul_mat_vec_q_stream_takes(groups, n_groups, k, in, rope);
+    if (in.planes && !streamed) {
         // a pending MoE combine and a consumer that is not the streamed kernel: evaluate it first, then the vector exists like any other
         moe_combine(in.pl_probs, in.pl_ids, in.n_planes, in.pl_mode, in.planes, (size_t) in.plane_stride*4, k, in.x, in.x_out, stream);
         in.x = in.x_out; in.planes = nullptr; in.n_planes = 0; in.x_out = nullptr; in.pl_probs = nullptr; in.pl_ids = nullptr;
+        streamed = mul_mat_vec_q_stream_takes(groups, n_groups, k, in, rope);
     }
-    if (mul_mat_vec_q_stream_takes(groups, n_groups, k, in, rope)) {      // the streamed kernel (mmvq_stream.h); callers do not pass it a `fin`
-        uint64_t wbytes = 0;
-        for (int i = 0; i < n_groups; i++) wbytes += (uint64_t) groups[i].m*groups[i].row_stride*(groups[i].epi == EPI_GLU ? 2 : 1);
-        if (g_hook.pre) g_hook.pre(g_hook.ctx, groups[0].type, wbytes, 1, k);
-        hipEvent_t e0 = mi355x_fused_ev0, e1 = mi355x_fused_ev1;
-        mi355x_fused_ev0 = nullptr; mi355x_fused_ev1 = nullptr;
-        mul_mat_vec_q_stream(groups, n_groups, k, in, rope, stream, e0, e1, &mi355x_fused_last_kernel);
-        if (g_hook.post) g_hook.post(g_hook.ctx, groups[0].type, wbytes, 1, k);
-        return;
-    }
-    const fused_launch L = fused_prepare(groups, n_groups, k, in, rope, fin);
-    if (g_hook.pre) g_hook.pre(g_hook.ctx, L.ta, L.wbytes, 1, L.k);
+    if (streamed) { mul_mat_vec_q_stream(groups, n_groups, k, in, rope, stream, rec); return; }      // (mmvq_stream.h); callers do not pass it a `fin`
+    fused_launch L = fused_prepare(groups, n_groups, k, in, rope, fin);
+    L.rec = rec;
     fused_launch_kernel(L, stream);
-    static const int dup = getenv("GGML_MI355X_DEBUG_DUP_LAUNCH") ? atoi(getenv("GGML_MI355X_DEBUG_DUP_LAUNCH")) : 0;     // timing experiments only (results are wrong where dst aliases the residual)
-    if (dup) {
-        fused_launch L2 = fused_prepare(groups, n_groups, k, in, rope, fin);      // (its own stamp slot in the -DMI_STAMPS build)
-        fused_launch_kernel(L2, stream);
-    }
-    if (g_hook.post) g_hook.post(g_hook.ctx, L.ta, L.wbytes, 1, L.k);
 }
 
 // which weight types may share one grouped launch (the mixtures llama_tensor_get_type produces, src/llama-quant.cpp:178-434)

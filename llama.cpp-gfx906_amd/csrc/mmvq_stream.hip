@@ -12,13 +12,13 @@
 
 namespace mi355x {
 
-template <int TA, int TB, bool GLU> static void st_launch_t(const st_args & a, int blocks, size_t lds, hipStream_t stream, hipEvent_t e0, hipEvent_t e1, const char ** kname) {
+template <int TA, int TB, bool GLU> static void st_launch_t(const st_args & a, int blocks, size_t lds, hipStream_t stream, mmvq_launch_rec * rec) {
     static char name[64] = "";
     if (!name[0]) snprintf(name, sizeof(name), "k_mmvq_stream<%d, %d, true, %s>", TA, TB, GLU ? "true" : "false");
-    *kname = name;
+    if (rec) rec->kernel = name;
     MI_LDS_LIMIT_OR_DIE(163840, k_mmvq_stream<TA, TB, true, GLU>);
-    if (e0) hipExtLaunchKernelGGL((k_mmvq_stream<TA, TB, true, GLU>), dim3((unsigned) blocks), dim3(ST_THREADS), lds, stream, e0, e1, 0, a);
-    else    hipLaunchKernelGGL((k_mmvq_stream<TA, TB, true, GLU>), dim3((unsigned) blocks), dim3(ST_THREADS), lds, stream, a);
+    if (rec && rec->e0) hipExtLaunchKernelGGL((k_mmvq_stream<TA, TB, true, GLU>), dim3((unsigned) blocks), dim3(ST_THREADS), lds, stream, rec->e0, rec->e1, 0, a);
+    else hipLaunchKernelGGL((k_mmvq_stream<TA, TB, true, GLU>), dim3((unsigned) blocks), dim3(ST_THREADS), lds, stream, a);
 }
 
 static int st_unit_bytes(int type) { return type == T_Q4_K ? 144 : type == T_Q5_K ? 176 : type == T_Q6_K ? 210 : type == T_Q8_0 ? 272 : type == T_Q4_0 ? 144 : type == ST_Q8_0_B10 ? 340 : type == ST_MXFP4_B10 ? 170 : 0; }
@@ -65,9 +65,8 @@ extern "C" int mi355x_stream_stamps_read(int slot, unsigned long long * out, int
 #endif
 
 bool mul_mat_vec_q_stream_enabled(void) {
-    static int on = -1;
-    if (on < 0) { const char * e = getenv("GGML_MI355X_STREAM"); on = e ? atoi(e) : 1; }
-    return on != 0;
+    static const bool on = env_on("GGML_MI355X_STREAM");
+    return on;
 }
 
 static int st_fill(const mmvq_group * groups, int n_groups, int64_t k, const mmvq_input & in, const mmvq_rope * rope, st_args & a,
@@ -114,7 +113,7 @@ bool mul_mat_vec_q_stream_takes(const mmvq_group * groups, int n_groups, int64_t
     if (S < (nslots_max < 2 ? nslots_max : 2)) return false;
     for (int i = 0; i < n_groups; i++) if ((int64_t) 256*groups[i].m >= (1ll << 31)) return false;      // (the kernel deals rows with 32-bit arithmetic: workgroups x row units)
     // experiment knob: launches that stream fewer bytes than this go to the register-ring kernel (is the streamed kernel's envelope a loss on the small launches?)
-    static const double min_bytes = getenv("GGML_MI355X_STREAM_MIN_MB") ? atof(getenv("GGML_MI355X_STREAM_MIN_MB"))*1e6 : 0.0;
+    static const double min_bytes = env_double("GGML_MI355X_STREAM_MIN_MB", 0.0)*1e6;
     if (min_bytes > 0.0 && bytes_total < min_bytes && !in.planes && !b10) {
         for (int i = 0; i < n_groups; i++) if (groups[i].eid || groups[i].epi == EPI_GLU || (groups[i].epi == EPI_ROPE && rope && (rope->p.mode & 2))) return true;
         return false;
@@ -138,9 +137,9 @@ static int st_fill(const mmvq_group * groups, int n_groups, int64_t k, const mmv
     // (measured, tg128 on one box, `profiles/r04_stream_early_sweep.log`: 0 slots 588.4 tok/s, 1 slot 616.5, 2 slots 613.9, 4 slots 603.3)
     // (not kept: one batch of scalar loads over the whole 928-byte argument block at entry, so that the compiler's ~9 dependent s_loads before the first vector load
     // hit the scalar cache — same box, alternating: 604 / 600 tok/s with the batch, 617 / 617 without: the chain was not missing)
-    { static const int early = getenv("GGML_MI355X_STREAM_EARLY") ? atoi(getenv("GGML_MI355X_STREAM_EARLY")) : 1;
-      static const int q16 = getenv("GGML_MI355X_STREAM_Q16") ? atoi(getenv("GGML_MI355X_STREAM_Q16")) : 1; 
-      static const int touch = getenv("GGML_MI355X_STREAM_XTOUCH") ? atoi(getenv("GGML_MI355X_STREAM_XTOUCH")) : 1; a.early = (early & 0xFF) | (q16 ? 0 : 0x100) | (touch ? 0 : 0x200); }
+    { static const int early = (int) env_int("GGML_MI355X_STREAM_EARLY", 1);
+      static const bool q16 = env_on("GGML_MI355X_STREAM_Q16"), touch = env_on("GGML_MI355X_STREAM_XTOUCH");
+      a.early = (early & 0xFF) | (q16 ? 0 : 0x100) | (touch ? 0 : 0x200); }
     if (in.mode == PRO_Q8) { a.a_qs = in.act.qs; a.a_d = in.act.d; a.a_bs = in.act.bsums; }
     if (rope) a.rope = make_fused_rope(*rope);
 
@@ -174,7 +173,7 @@ static int st_fill(const mmvq_group * groups, int n_groups, int64_t k, const mmv
     }
     // NEOX groups as two row streams (mmvq_stream.h: st_group::neox2): the smallest number of pairs per workgroup c for which every such group gets EXACTLY m/2/c
     // workgroups and the launch still fits the chip; the other groups share what is left
-    static const bool neox2_on = !getenv("GGML_MI355X_NEOX2") || atoi(getenv("GGML_MI355X_NEOX2")) != 0;
+    static const bool neox2_on = env_on("GGML_MI355X_NEOX2");
     if (neox2_on && rope && (rope->p.mode & 2) && rope->head_dim >= 16) {
         const int hh = rope->head_dim/2;
         for (int c = 4; c < hh; c *= 2) {
@@ -223,9 +222,8 @@ static int st_fill(const mmvq_group * groups, int n_groups, int64_t k, const mmv
 }
 
 void mul_mat_vec_q_stream(const mmvq_group * groups, int n_groups, int64_t k, const mmvq_input & in, const mmvq_rope * rope, hipStream_t stream,
-                          hipEvent_t e0, hipEvent_t e1, const char ** kname) {
-    static int ring_env = -1;
-    if (ring_env < 0) { const char * r = getenv("GGML_MI355X_STREAM_RING"); ring_env = r ? atoi(r) : 0; }
+                          mmvq_launch_rec * rec) {
+    static const int ring_env = (int) env_int("GGML_MI355X_STREAM_RING", 0);
     st_args a; size_t fixed_max; int slot_max, nslots_max, npart_max, ta, tb; double bytes_total;
     const int blocks = st_fill(groups, n_groups, k, in, rope, a, fixed_max, slot_max, nslots_max, npart_max, ta, tb, bytes_total);
     int S = (int)((163840 - (int64_t) fixed_max)/slot_max);
@@ -246,18 +244,18 @@ void mul_mat_vec_q_stream(const mmvq_group * groups, int n_groups, int64_t k, co
     }
 #endif
     const bool glu = n_groups == 1 && groups[0].epi == EPI_GLU;
-    if (ta == T_Q4_K && tb == T_Q4_K)      { if (glu) st_launch_t<T_Q4_K, T_Q4_K, true>(a, blocks, lds, stream, e0, e1, kname); else st_launch_t<T_Q4_K, T_Q4_K, false>(a, blocks, lds, stream, e0, e1, kname); }
-    else if (ta == T_Q5_K && tb == T_Q5_K) { if (glu) st_launch_t<T_Q5_K, T_Q5_K, true>(a, blocks, lds, stream, e0, e1, kname); else st_launch_t<T_Q5_K, T_Q5_K, false>(a, blocks, lds, stream, e0, e1, kname); }
-    else if (ta == T_Q6_K && tb == T_Q6_K) { if (glu) st_launch_t<T_Q6_K, T_Q6_K, true>(a, blocks, lds, stream, e0, e1, kname); else st_launch_t<T_Q6_K, T_Q6_K, false>(a, blocks, lds, stream, e0, e1, kname); }
-    else if (ta == ST_Q8_0_B10)  { if (glu) st_launch_t<ST_Q8_0_B10, ST_Q8_0_B10, true>(a, blocks, lds, stream, e0, e1, kname); else st_launch_t<ST_Q8_0_B10, ST_Q8_0_B10, false>(a, blocks, lds, stream, e0, e1, kname); }
-    else if (ta == ST_MXFP4_B10) { if (glu) st_launch_t<ST_MXFP4_B10, ST_MXFP4_B10, true>(a, blocks, lds, stream, e0, e1, kname); else st_launch_t<ST_MXFP4_B10, ST_MXFP4_B10, false>(a, blocks, lds, stream, e0, e1, kname); }
-    else if (ta == T_Q4_0 && tb == T_Q4_0) { if (glu) st_launch_t<T_Q4_0, T_Q4_0, true>(a, blocks, lds, stream, e0, e1, kname); else st_launch_t<T_Q4_0, T_Q4_0, false>(a, blocks, lds, stream, e0, e1, kname); }
-    else if (ta == T_Q8_0 && tb == T_Q8_0) { if (glu) st_launch_t<T_Q8_0, T_Q8_0, true>(a, blocks, lds, stream, e0, e1, kname); else st_launch_t<T_Q8_0, T_Q8_0, false>(a, blocks, lds, stream, e0, e1, kname); }
-    else if (ta == T_Q8_0 && tb == T_Q4_K) st_launch_t<T_Q8_0, T_Q4_K, false>(a, blocks, lds, stream, e0, e1, kname);
-    else if (ta == T_Q8_0 && tb == T_Q6_K) st_launch_t<T_Q8_0, T_Q6_K, false>(a, blocks, lds, stream, e0, e1, kname);
-    else if (ta == T_Q4_K && tb == T_Q5_K) st_launch_t<T_Q4_K, T_Q5_K, false>(a, blocks, lds, stream, e0, e1, kname);
-    else if (ta == T_Q4_K && tb == T_Q6_K) st_launch_t<T_Q4_K, T_Q6_K, false>(a, blocks, lds, stream, e0, e1, kname);
-    else if (ta == T_Q5_K && tb == T_Q6_K) st_launch_t<T_Q5_K, T_Q6_K, false>(a, blocks, lds, stream, e0, e1, kname);
+    if (ta == T_Q4_K && tb == T_Q4_K)      { if (glu) st_launch_t<T_Q4_K, T_Q4_K, true>(a, blocks, lds, stream, rec); else st_launch_t<T_Q4_K, T_Q4_K, false>(a, blocks, lds, stream, rec); }
+    else if (ta == T_Q5_K && tb == T_Q5_K) { if (glu) st_launch_t<T_Q5_K, T_Q5_K, true>(a, blocks, lds, stream, rec); else st_launch_t<T_Q5_K, T_Q5_K, false>(a, blocks, lds, stream, rec); }
+    else if (ta == T_Q6_K && tb == T_Q6_K) { if (glu) st_launch_t<T_Q6_K, T_Q6_K, true>(a, blocks, lds, stream, rec); else st_launch_t<T_Q6_K, T_Q6_K, false>(a, blocks, lds, stream, rec); }
+    else if (ta == ST_Q8_0_B10)  { if (glu) st_launch_t<ST_Q8_0_B10, ST_Q8_0_B10, true>(a, blocks, lds, stream, rec); else st_launch_t<ST_Q8_0_B10, ST_Q8_0_B10, false>(a, blocks, lds, stream, rec); }
+    else if (ta == ST_MXFP4_B10) { if (glu) st_launch_t<ST_MXFP4_B10, ST_MXFP4_B10, true>(a, blocks, lds, stream, rec); else st_launch_t<ST_MXFP4_B10, ST_MXFP4_B10, false>(a, blocks, lds, stream, rec); }
+    else if (ta == T_Q4_0 && tb == T_Q4_0) { if (glu) st_launch_t<T_Q4_0, T_Q4_0, true>(a, blocks, lds, stream, rec); else st_launch_t<T_Q4_0, T_Q4_0, false>(a, blocks, lds, stream, rec); }
+    else if (ta == T_Q8_0 && tb == T_Q8_0) { if (glu) st_launch_t<T_Q8_0, T_Q8_0, true>(a, blocks, lds, stream, rec); else st_launch_t<T_Q8_0, T_Q8_0, false>(a, blocks, lds, stream, rec); }
+    else if (ta == T_Q8_0 && tb == T_Q4_K) st_launch_t<T_Q8_0, T_Q4_K, false>(a, blocks, lds, stream, rec);
+    else if (ta == T_Q8_0 && tb == T_Q6_K) st_launch_t<T_Q8_0, T_Q6_K, false>(a, blocks, lds, stream, rec);
+    else if (ta == T_Q4_K && tb == T_Q5_K) st_launch_t<T_Q4_K, T_Q5_K, false>(a, blocks, lds, stream, rec);
+    else if (ta == T_Q4_K && tb == T_Q6_K) st_launch_t<T_Q4_K, T_Q6_K, false>(a, blocks, lds, stream, rec);
+    else if (ta == T_Q5_K && tb == T_Q6_K) st_launch_t<T_Q5_K, T_Q6_K, false>(a, blocks, lds, stream, rec);
     else { fprintf(stderr, "mul_mat_vec_q_stream: type pair (%d, %d) has no kernel\n", ta, tb); abort(); }
 }
 

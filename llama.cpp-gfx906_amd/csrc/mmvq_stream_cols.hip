@@ -165,8 +165,7 @@ static void stc_launch(const st_args & a, const st_cols & c, int blocks, size_t 
 // false = not taken (format, shape, LDS): the caller runs another kernel
 bool mul_mat_vec_q_stream_cols(int type_a, const void * W, size_t w_row_stride, int64_t m, int64_t k,
                                const act_q8 & act, int64_t n, float * dst, size_t dst_col_stride_bytes, hipStream_t stream) {
-    static int on = -1;
-    if (on < 0) { const char * e = getenv("GGML_MI355X_STREAM_COLS"); on = e ? atoi(e) : 1; }
+    static const int on = (int) env_int("GGML_MI355X_STREAM_COLS", 1);
     if (!on || !mul_mat_vec_q_stream_enabled() || n < 2 || n > 8 || act.kind != T_Q8_K) return false;
     // Q6_K: built and tested (GGML_MI355X_STREAM_COLS=2 routes it here), not routed by default — its unit costs twice the vector instructions of
     // Q4_K's per column (6-bit unpack, 16-element scale groups) and the kernel is instruction-bound from 3 columns on: 23.7 / 24.1 / 39.9 us at

@@ -600,6 +600,52 @@ def test_two_backends_from_two_threads():
         assert np.array_equal(single[i], multi[i])
 
 
+def test_two_backends_profile_from_two_threads():
+    """Option "profile" = 1 on two backends driven concurrently from two threads: what a grouped mat-vec launch is timed with and which kernel it
+    used travel in the call itself, so each backend's profile — (type, m, k, n, launches, bytes_per_launch, kernel) per entry — must equal what the
+    same backend records when it runs alone, and every grouped entry (m < 0) must name its kernel. The logits must agree too."""
+    import threading
+    seqs = {0: [[3, 4, 5, 6, 9, 11, 200]] + [[t] for t in range(10, 40)], 1: [list(range(50, 90))] + [[t] for t in range(100, 130)]}
+    keys = ("type", "m", "k", "n", "launches", "bytes_per_launch", "kernel")
+
+    def run(idx, out):
+        be = gg.Backend(0)
+        try:
+            m = ls.SynthLlama(be, "tiny" if idx == 0 else "tiny-moe", "Q4_K_M", n_ctx=96, seed=11 + idx)
+            be.set_option("profile", 1)
+            logits = np.stack([m.decode(t).copy() for t in seqs[idx]])
+            prof = sorted(tuple(e[k] for k in keys) for e in be.profile(256))
+            be.set_option("profile", 0)
+            out[idx] = (logits, prof)
+            m.free()
+        finally:
+            be.free()
+
+    single = {}
+    for i in (0, 1):
+        run(i, single)
+    multi = {}
+    errs = []
+    def guarded(i):
+        try:
+            run(i, multi)
+        except Exception as e:   # noqa: BLE001
+            errs.append(e)
+    ths = [threading.Thread(target=guarded, args=(i,)) for i in (0, 1)]
+    for t in ths:
+        t.start()
+    for t in ths:
+        t.join()
+    assert not errs, errs
+    for i in (0, 1):
+        grouped = [e for e in single[i][1] if e[1] < 0]
+        assert grouped, "the run made no grouped mat-vec launch"
+        for prof in (single[i][1], multi[i][1]):
+            assert all(e[6] for e in prof if e[1] < 0), prof
+        assert single[i][1] == multi[i][1]
+        assert np.array_equal(single[i][0], multi[i][0])
+
+
 @pytest.mark.parametrize("env,value", [("GGML_MI355X_STREAM", "0"), ("GGML_MI355X_GRAPH_SEG0", "0"), ("GGML_MI355X_UPLOAD_BATCH", "0"), ("GGML_MI355X_STREAM_EARLY", "0"), ("GGML_MI355X_STREAM_EARLY", "3"),
                                        ("GGML_MI355X_STREAM_Q16", "0"), ("GGML_MI355X_STREAM_XTOUCH", "0")])
 def test_other_decode_arrangements_stay_correct(env, value):

@@ -37,8 +37,8 @@ int main() {
         mmvq_input in = {}; in.mode = PRO_QUANT; in.x = x; in.act_kind = T_Q8_K;
         if (!mul_mat_vec_q_stream_takes(&gA, 1, K, in, nullptr) || !mul_mat_vec_q_stream_takes(&gB, 1, K, in, nullptr)) { printf("not taken\n"); return 1; }
         // B's descriptor: launch it once
-        const char * kn = nullptr; mmvq_next descB;
-        mul_mat_vec_q_stream(&gB, 1, K, in, nullptr, st, nullptr, nullptr, &kn); mul_mat_vec_q_stream_last_desc(&descB);
+        mmvq_next descB;
+        mul_mat_vec_q_stream(&gB, 1, K, in, nullptr, st); mul_mat_vec_q_stream_last_desc(&descB);
         CK(hipStreamSynchronize(st));
         printf("%s (B's descriptor: %d group(s), %d bytes per workgroup)\n", s.name, descB.n_groups, descB.bytes);
         for (int variant = 0; variant < 3; variant++) {      // 0: no prefetch; 1: A prefetches B; 2: again no prefetch
@@ -47,9 +47,9 @@ int main() {
             for (int r = 0; r < 12; r++) {
                 hipLaunchKernelGGL(k_evict, dim3(2048), dim3(256), 0, st, (const int4v_ *) E, EV/16, sink);
                 mmvq_next none = {}; mul_mat_vec_q_stream_set_next(pf ? &descB : &none);
-                mul_mat_vec_q_stream(&gA, 1, K, in, nullptr, st, nullptr, nullptr, &kn);
+                mul_mat_vec_q_stream(&gA, 1, K, in, nullptr, st);
                 mul_mat_vec_q_stream_set_next(&none);
-                mul_mat_vec_q_stream(&gB, 1, K, in, nullptr, st, e0, e1, &kn);
+                mmvq_launch_rec rec = { e0, e1, nullptr }; mul_mat_vec_q_stream(&gB, 1, K, in, nullptr, st, &rec);
                 CK(hipStreamSynchronize(st));
                 float ms; CK(hipEventElapsedTime(&ms, e0, e1));
                 if (r >= 2) tb.push_back(ms*1e3f);
