@@ -226,6 +226,11 @@ void attn_prefill(const void * q, size_t q_nb1, size_t q_nb2, const void * k, si
                   uint16_t * y16 = nullptr,      // y16 != NULL: also (dst == NULL: only) the bf16 copy the following mat-mul reads, rows of hd*n_head (a multiple of 64)
                   const attn_extra * ex = nullptr);     // (K and V are f16 here: other cache types are converted by kv_to_f16 first)
 
+// the persistent kernels run one workgroup per CU: the current device's CU count, asked for once (mmvq_fused.hip)
+int device_cu_count();
+// the dynamic LDS a workgroup of the streamed kernels may use: a CU's 160 KiB
+constexpr int MI_LDS_BUDGET = 160*1024;
+
 // grouped mat-vec (n = 1): up to MMVQ_MAX_GROUPS weight tensors that share one activation vector, each with an epilogue
 constexpr int MMVQ_MAX_GROUPS = 4;
 enum mmvq_epilogue { EPI_NONE = 0, EPI_ADD = 1, EPI_ROPE = 2, EPI_GLU = 3 };
@@ -288,9 +293,7 @@ void mul_mat_vec_q_fused(const mmvq_group * groups, int n_groups, int64_t k, con
 // the streamed form of the grouped launch (mmvq_stream.h: loader wave + LDS slot ring + one 256-weight unit per lane): K-quant weights in
 // contiguous rows, no expert stacks; mul_mat_vec_q_fused routes to it when mul_mat_vec_q_stream_takes says so (it never writes an mmvq_fin image)
 bool mul_mat_vec_q_stream_enabled(void);       // GGML_MI355X_STREAM (default 1)
-bool mul_mat_vec_q_stream_takes(const mmvq_group * groups, int n_groups, int64_t k, const mmvq_input & in, const mmvq_rope * rope);
-void mul_mat_vec_q_stream(const mmvq_group * groups, int n_groups, int64_t k, const mmvq_input & in, const mmvq_rope * rope, hipStream_t stream,
-                          mmvq_launch_rec * rec = nullptr);
+bool mul_mat_vec_q_stream_takes(const mmvq_group * groups, int n_groups, int64_t k, const mmvq_input & in, const mmvq_rope * rope);     // = the launch's plan is ok (mmvq_stream.h: st_plan)
 bool mul_mat_vec_q_fused_fin_supported(int64_t m, int64_t k_in);   // may a GLU launch with m output rows carry an mmvq_fin
 
 // ---- small uploads batched into one launch (backend.cpp: be_set_tensor_async / uploads_flush) ----

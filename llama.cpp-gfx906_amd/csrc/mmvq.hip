@@ -226,14 +226,9 @@ template <int TYPE, int NCOLS>
 static bool launch_mmvq_cols(const mmvq_args & a, int act_kind, hipStream_t stream) {
     const size_t lds = (size_t) NCOLS*lds_bytes_for(act_kind, a.k);
     if (lds > 150*1024 || a.k % 16 != 0 || a.m >= (1ll << 30)) return false;
-    static int n_cu = 0;
-    if (n_cu == 0) {
-        int dev = 0; hipDeviceProp_t prop;
-        n_cu = hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess ? prop.multiProcessorCount : 256;
-    }
     if (!MI_LDS_LIMIT(152*1024, k_mmvq_cols<TYPE, NCOLS>)) return false;
     const int64_t pairs = (a.m + 1)/2;
-    const int blocks = (int) std::min<int64_t>(n_cu, (pairs + 7)/8);
+    const int blocks = (int) std::min<int64_t>(device_cu_count(), (pairs + 7)/8);
     hipLaunchKernelGGL((k_mmvq_cols<TYPE, NCOLS>), dim3((unsigned) blocks), dim3(512), lds, stream, a);
     return true;
 }

@@ -306,12 +306,7 @@ __global__ void __launch_bounds__(512, 1) k_mmvq_cols_mfma(const colmf_args p) {
 template <int TYPE>
 static bool launch_cols_mfma(colmf_args & a, size_t lds, hipStream_t stream) {
     if (!MI_LDS_LIMIT(156*1024, k_mmvq_cols_mfma<TYPE>)) return false;
-    static int n_cu = 0;
-    if (n_cu == 0) {
-        int dev = 0; hipDeviceProp_t prop;
-        n_cu = hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess ? prop.multiProcessorCount : 256;
-    }
-    const int blocks = std::min(n_cu, a.n_tiles);
+    const int blocks = std::min(device_cu_count(), a.n_tiles);
     hipLaunchKernelGGL((k_mmvq_cols_mfma<TYPE>), dim3((unsigned) blocks), dim3(512), lds, stream, a);
     return true;
 }

@@ -3,6 +3,7 @@
 // block, picks the kernel family. Every launch is issued inside the call; what a caller wants timed or named travels in the call's mmvq_launch_rec.
 // No mutable state outside the -DMI_STAMPS diagnostic build.
 #include "mmvq_fused.h"
+#include "mmvq_stream.h"      // st_plan
 
 #include <limits.h>
 
@@ -47,7 +48,7 @@ bool mul_mat_vec_q_fused_supported(int64_t k, int act_kind) {
 }
 bool mul_mat_vec_q_fused_prologue_supported(int64_t k, int act_kind) { return (k % 256 == 0 || (act_kind == T_Q8_0 && k % 32 == 0)) && k <= 16*1024; }
 
-static int device_cu_count() {
+int device_cu_count() {
     static int n_cu = 0;
     if (n_cu == 0) {
         int dev = 0; hipDeviceProp_t prop;
@@ -246,14 +247,14 @@ static void fused_launch_kernel(const fused_launch & L, hipStream_t stream) {
 void mul_mat_vec_q_fused(const mmvq_group * groups, int n_groups, int64_t k, const mmvq_input & in_, const mmvq_rope * rope, hipStream_t stream,
                          const mmvq_fin * fin, mmvq_launch_rec * rec) {
     mmvq_input in = in_;
-    bool streamed = mul_mat_vec_q_stream_takes(groups, n_groups, k, in, rope);
-    if (in.planes && !streamed) {
-        // a pending MoE combine and a consumer that is not the streamed kernel: evaluate it first, then the vector exists like any other
+    st_plan plan = mul_mat_vec_q_stream_plan(groups, n_groups, k, in, rope);
+    if (in.planes && !plan.ok) {
+        // a pending MoE combine and a consumer that is not the streamed kernel: evaluate it first, then the vector exists like any other (and the launch is planned again)
         moe_combine(in.pl_probs, in.pl_ids, in.n_planes, in.pl_mode, in.planes, (size_t) in.plane_stride*4, k, in.x, in.x_out, stream);
         in.x = in.x_out; in.planes = nullptr; in.n_planes = 0; in.x_out = nullptr; in.pl_probs = nullptr; in.pl_ids = nullptr;
-        streamed = mul_mat_vec_q_stream_takes(groups, n_groups, k, in, rope);
+        plan = mul_mat_vec_q_stream_plan(groups, n_groups, k, in, rope);
     }
-    if (streamed) { mul_mat_vec_q_stream(groups, n_groups, k, in, rope, stream, rec); return; }      // (mmvq_stream.h); callers do not pass it a `fin`
+    if (plan.ok) { mul_mat_vec_q_stream(plan, stream, rec); return; }      // (mmvq_stream.h); callers do not pass it a `fin`
     fused_launch L = fused_prepare(groups, n_groups, k, in, rope, fin);
     L.rec = rec;
     fused_launch_kernel(L, stream);

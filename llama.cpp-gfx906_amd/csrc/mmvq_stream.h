@@ -17,7 +17,9 @@
 //     LDS, and after the last slot the consumers add each row's partials in a fixed order and run the epilogue with a lane per ROW (or
 //     rotation pair): residual, rotation, SwiGLU, cache stores — no single-live-lane epilogues.
 // Synchronisation inside the workgroup is by words in LDS (landed / done counters, polled with s_sleep): the loader cannot stand at an
-// s_barrier while it is issuing, so after the first barrier (activation loads are queued before any weight) nobody uses one.
+// s_barrier while it is issuing, so after the one barrier (activation loads are queued before any weight) nobody uses one.
+// A launch is ONE phase: every workgroup builds one activation image, streams one slot sequence (numbered from 0) and runs one epilogue, so
+// every counter below starts at zero and each meeting point is met exactly once.
 #pragma once
 
 #include "mmvq_core.h"
@@ -28,7 +30,7 @@ namespace mi355x {
 
 constexpr int ST_NC = 8;                 // consumer waves
 constexpr int ST_THREADS = (ST_NC + 1)*64;
-constexpr int ST_SYNC_WORDS = 64;        // [0] slots landed, [2] image parts ready, [3] consumers finished, [4] norm partials ready, [16 + s] done[s]
+constexpr int ST_SYNC_WORDS = 64;        // [0] slots landed; consumer waves arrived with [2] the image, [3] the last slot, [4] the norm's partial sums; [16 + s]: slots consumed out of ring slot s
 constexpr int ST_MAX_RING = 48;          // slots
 // the activation of one 256-block as the consumers read it: 16 chunks of int8; one chunk with the eight 32-element sums split into (h, l)
 // signed bytes, sum = 128 h + l (so that sum_j m_j * bsum_j is 4-byte dots); two chunks with the sixteen 16-element sums split the same way
@@ -72,7 +74,7 @@ struct st_args {
     int n_groups, k, nb, mode;                // nb: units per row (k / 256, or k / 320 for the ten-block units)
     int nchunk, act_stride;                   // 256-element pieces of the activation vector ((k + 255) / 256); bytes between the image's units
     int block_end[MMVQ_MAX_GROUPS];
-    uint32_t magic; int S; float eps; int early;     // early: slots of the first phase the loader issues BEFORE it meets the consumers at the first barrier (0: none)
+    uint32_t magic; int S; float eps; int early;     // early: slots the loader issues BEFORE it meets the consumers at the workgroup's barrier (0: none)
     const float * x; const float * norm_w;
     const int8_t * a_qs; const float * a_d; const int16_t * a_bs;      // PRO_Q8: the n = 1 image act_q8_carve lays out
     fused_rope rope;
@@ -136,12 +138,11 @@ static __device__ __forceinline__ void st_wait_ge(const uint32_t * w, uint32_t t
     while (st_poll_ld(w) < target) __builtin_amdgcn_s_sleep(1);
     asm volatile("" ::: "memory");      // nothing that reads what the word guards moves above the wait
 }
-// every consumer wave arrives once at counter w (its LDS writes drained first), then waits for all of them
-// (the counters are cumulative: the n-th meeting at w, n = 0, 1, ..., waits for (n + 1)*ST_NC arrivals)
-static __device__ __forceinline__ void st_consumers_meet(uint32_t * w, int lane, int n) {
+// every consumer wave arrives once at counter w (its LDS writes drained first), then waits for all of them; each counter is met once per launch
+static __device__ __forceinline__ void st_consumers_meet(uint32_t * w, int lane) {
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     if (lane == 0) st_flag_add(w, 1u);
-    st_wait_ge(w, (uint32_t)(n + 1)*ST_NC);
+    st_wait_ge(w, (uint32_t) ST_NC);
 }
 
 // ---- per-format unit: UB bytes of packed weights = 256 weights; one lane consumes one unit ----
@@ -459,32 +460,25 @@ static __device__ __forceinline__ void st_rows(const st_group & g, int wg, int n
     R = (wg == nwg - 1 ? g.m : (int)((((uint32_t) wg + 1u)*nru/(uint32_t) nwg)*(uint32_t) g.ralign)) - r0;
 }
 
-// ================= the loader's share of one phase: slots slot0 .. slot0 + nslots of the workgroup's slot sequence =================
+// ================= the loader: the workgroup's slots 0 .. nslots, in order =================
 // In flight: at most ST_INFLIGHT pieces behind the slot being issued (a wave counts at most 63 outstanding loads; a slot is at most 14).
-// Which slots have LANDED follows from the piece count alone — after `s_waitcnt vmcnt(N)` all but the youngest N pieces are in LDS — and
-// the pieces a slot ends at are kept per slot (cum[]: phases of a chain have slots of different sizes).
+// Which slots have LANDED follows from the piece count alone — after `s_waitcnt vmcnt(N)` all but the youngest N pieces are in LDS.
 constexpr int ST_INFLIGHT = 36;
 // Everything here is wave-uniform and must stay in scalar registers and out of memory: the loader is the critical path of the whole kernel
 // (a version that kept a per-slot table — in LDS, then in an array the compiler moved to vector registers — and re-read the group's
-// pointers from the kernel arguments every slot lost a sixth of the stream rate). So: slots of ONE phase have one size, and which of them
-// have landed is arithmetic on the piece count; of the phase before, the same with its own size; anything older has landed for sure
-// because a phase that issued fewer than ST_INFLIGHT pieces is followed by a full drain.
+// pointers from the kernel arguments every slot lost a sixth of the stream rate). So: the slots of a launch have one size, and which of
+// them have landed is arithmetic on the piece count.
 struct st_loader_state {
-    int landed, pieces;                       // slots published; pieces issued so far
-    int c_slot0, c_base, p_slot0, p_base, p_magic, c_pps;      // the current / the previous phase: its first slot, the pieces issued before it; 65536 / pieces-per-slot (rounded up) of the previous one
+    int landed, pieces, pps;      // slots published; pieces issued so far; pieces per slot
 };
 template <int PPS>
 static __device__ __forceinline__ void st_loader_publish(const st_lds & L, st_loader_state & s, int issued_slots, int outstanding, int lane) {
-    const int done = s.pieces - outstanding;
-    int l;
-    if (done >= s.c_base) l = s.c_slot0 + (done - s.c_base)/PPS;
-    else if (done >= s.p_base) l = s.p_slot0 + (((done - s.p_base)*s.p_magic) >> 16);
-    else l = s.p_slot0;
-    l = min(l, issued_slots);
+    const int l = min((s.pieces - outstanding)/PPS, issued_slots);
     if (l > s.landed) { s.landed = l; if (lane == 0) st_flag_st(&L.sync[0], (uint32_t) l); }
 }
+// issues every slot (ls: zeroed by the caller); st_loader_drain then publishes what is still in flight
 template <int TYPE, bool NT>
-static __device__ __forceinline__ void st_loader_phase(const st_args & p, const st_group & g, int wg, int nwg, const st_lds & L, int slot0, st_loader_state & ls, int lane, int expert, int barrier_after = 0) {
+static __device__ __forceinline__ void st_loader_issue(const st_args & p, const st_group & g, int wg, int nwg, const st_lds & L, st_loader_state & ls, int lane, int expert, int barrier_after = 0) {
     typedef st_unit<TYPE> U;
     constexpr int PPS = (64*U::UB + 1023)/1024;
     const int nb = p.nb;
@@ -493,12 +487,7 @@ static __device__ __forceinline__ void st_loader_phase(const st_args & p, const 
     const int n1 = R*nb, ns1 = (n1 + 63) >> 6, nslots = GLU ? 2*ns1 : ns1;
     const int S = L.S;
     const uint32_t voff = lane*16;
-    // a new phase: the one before becomes "previous"; if it was short, nothing of it (or of anything older) may stay unpublished
-    if (ls.pieces - ls.c_base < ST_INFLIGHT && ls.pieces > 0) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        if (slot0 > ls.landed) { ls.landed = slot0; if (lane == 0) st_flag_st(&L.sync[0], (uint32_t) slot0); }
-    }
-    ls.p_slot0 = ls.c_slot0; ls.p_base = ls.c_base; ls.c_slot0 = slot0; ls.c_base = ls.pieces; ls.c_pps = PPS;
+    ls.pps = PPS;
     const long long row_off = (long long) r0*nb*U::UB;
     const long long e_off = g.eid ? (long long) expert*g.estride : 0;      // (the expert the router picked: read on the device — k_mmvq_stream requests it before the first barrier)
     const char * const w0 = g.W + e_off + row_off; const char * const w1 = GLU ? g.W2 + e_off + row_off : w0;
@@ -506,16 +495,15 @@ static __device__ __forceinline__ void st_loader_phase(const st_args & p, const 
     // whose size is not a multiple of 16 ends inside that chunk: it is read in place — up to 15 bytes of the zeroed padding every quantized tensor of this
     // backend's buffers carries (MI_TENSOR_PAD) — and only chunks that start past the end are redirected to it
     const long long lim_all = (((long long) g.m*nb*U::UB - row_off - 1) & ~15ll);
-    int ring_i = slot0 % S;
+    int ring_i = 0;
     for (int i = 0; i < nslots; i++) {
-        const int gi = slot0 + i;                            // slot number in the workgroup's sequence
         const int si = GLU ? (i >= ns1) : 0, il = i - si*ns1;
         const char * gb = (si ? w1 : w0) + (long long) il*(64*U::UB);
-        if (gi >= S) {
+        if (i >= S) {
             // the ring slot must have been consumed; publish what is in flight first so that nobody waits for us meanwhile
-            if (st_poll_ld(&L.sync[16 + ring_i]) < (uint32_t)(gi - S + 1)) {
-                if (ls.landed < gi) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); ls.landed = gi; if (lane == 0) st_flag_st(&L.sync[0], (uint32_t) gi); }
-                st_wait_ge(&L.sync[16 + ring_i], (uint32_t)(gi - S + 1));
+            if (st_poll_ld(&L.sync[16 + ring_i]) < (uint32_t)(i - S + 1)) {
+                if (ls.landed < i) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); ls.landed = i; if (lane == 0) st_flag_st(&L.sync[0], (uint32_t) i); }
+                st_wait_ge(&L.sync[16 + ring_i], (uint32_t)(i - S + 1));
             }
         }
         const uint32_t dst = L.ring_a + (uint32_t) ring_i*L.slot_stride;
@@ -525,26 +513,25 @@ static __device__ __forceinline__ void st_loader_phase(const st_args & p, const 
         } else st_dma_slot<NT, PPS>(gb, voff, dst);
         ls.pieces += PPS;
         if (++ring_i == S) ring_i = 0;
-        // (barrier_after > 0: the workgroup's first barrier — behind which the consumers' activation loads are queued — is met after this many slots are on their way)
+        // (barrier_after > 0: the workgroup's one barrier — behind which the consumers' activation loads are queued — is met after this many slots are on their way)
         if (barrier_after > 0 && i + 1 == barrier_after) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); __builtin_amdgcn_s_barrier(); }
         asm volatile("s_waitcnt vmcnt(%0)" :: "n"(ST_INFLIGHT) : "memory");
-        if (ls.pieces > ST_INFLIGHT) st_loader_publish<PPS>(L, ls, gi + 1, ST_INFLIGHT, lane);
+        if (ls.pieces > ST_INFLIGHT) st_loader_publish<PPS>(L, ls, i + 1, ST_INFLIGHT, lane);
     }
     if (barrier_after > nslots) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); __builtin_amdgcn_s_barrier(); }      // (fewer slots than that: the barrier is still met once)
-    ls.p_magic = (65536 + PPS - 1)/PPS;       // (for the phase after this one)
 }
-// after the last phase: everything lands
-static __device__ __forceinline__ void st_loader_drain(const st_lds & L, int nslots_total, st_loader_state & ls, int lane) {
+// after the last slot is issued: everything lands
+static __device__ __forceinline__ void st_loader_drain(const st_lds & L, int nslots, st_loader_state & ls, int lane) {
     asm volatile("s_waitcnt vmcnt(18)" ::: "memory");
-    { const int done = ls.pieces - 18; const int l = min(nslots_total, done >= ls.c_base ? ls.c_slot0 + (done - ls.c_base)/max(ls.c_pps, 1) : ls.c_slot0);
+    { const int done = ls.pieces - 18; const int l = min(nslots, done >= 0 ? done/max(ls.pps, 1) : 0);
       if (l > ls.landed) { ls.landed = l; if (lane == 0) st_flag_st(&L.sync[0], (uint32_t) l); } }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if (nslots_total > ls.landed) { ls.landed = nslots_total; if (lane == 0) st_flag_st(&L.sync[0], (uint32_t) nslots_total); }
+    if (nslots > ls.landed) { ls.landed = nslots; if (lane == 0) st_flag_st(&L.sync[0], (uint32_t) nslots); }
 }
 
-// ---- the activation image of a phase ----
+// ---- the activation image ----
+// (every form requests its loads, then takes the workgroup's one barrier — the loader starts its stream behind those requests — and builds the image)
 // PRO_Q8: a Q8_K image some earlier launch made (act_q8_carve layout), re-laid for the consumers
-template <bool FIRST>
 static __device__ __forceinline__ void st_prologue_q8(const st_args & p, const st_lds & L, int ctid) {
     const int nb = p.nb, nq = p.k >> 4;
     int4v areg[2], breg[2];
@@ -553,7 +540,7 @@ static __device__ __forceinline__ void st_prologue_q8(const st_args & p, const s
     const int ibl = min(ctid, nb - 1);
     breg[0] = *(const int4v *) (p.a_bs + (size_t) ibl*16); breg[1] = *(const int4v *) (p.a_bs + (size_t) ibl*16 + 8);
     const float dreg = p.a_d[ibl];
-    if (FIRST) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); __builtin_amdgcn_s_barrier(); }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); __builtin_amdgcn_s_barrier();
 #pragma unroll
     for (int i = 0; i < 2; i++) {
         const int q = ctid + i*ST_NC*64;
@@ -582,8 +569,8 @@ static __device__ __forceinline__ void st_prologue_q8(const st_args & p, const s
 // the dependent chains of the wave-wide maxima and sums interleave — chunk after chunk behind a branch each cost ~0.5 us per chunk
 // IMG: 0 = Q8_K blocks (K-quant weights); 1 = the workgroup's weights are Q8_0 in 256-weight units — the image is the CPU path's Q8_0 instead (32-element
 // blocks, f16-rounded scales: quant_core.h); 2 = the same Q8_0 activation for the ten-block units (k % 256 != 0: the last 256-piece is partial)
-template <int NA, bool FIRST, int IMG, bool NORM>
-static __device__ __forceinline__ void st_prologue_f32(const st_args & p, const st_lds & L, int x_off, int seq, int & n_norm, int lane, int wave) {
+template <int NA, int IMG, bool NORM>
+static __device__ __forceinline__ void st_prologue_f32(const st_args & p, const st_lds & L, int x_off, int lane, int wave) {
     constexpr bool Q80 = IMG != 0;
     const int nchunk = p.nchunk;
     constexpr bool norm = NORM;        // (compile-time: see st_prologue_q8k16)
@@ -616,7 +603,7 @@ static __device__ __forceinline__ void st_prologue_f32(const st_args & p, const 
                     pr[u] = 0.0f; idv[u] = 0;
                     if (u < p.n_planes) { if (p.pl_ids) idv[u] = p.pl_ids[u]; else pr[u] = p.pl_probs[u]; }      // (pl_ids == NULL: the router's values in slot order)
                 }
-                if (FIRST) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); __builtin_amdgcn_s_barrier(); }
+                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); __builtin_amdgcn_s_barrier();
                 if (p.pl_ids) {
 #pragma unroll
                     for (int u = 0; u < 8; u++) if (u < p.n_planes) pr[u] = p.pl_probs[idv[u]];
@@ -652,14 +639,13 @@ static __device__ __forceinline__ void st_prologue_f32(const st_args & p, const 
                 const int c = wave + ST_NC*i;
                 if (blockIdx.x == 0 && c < nchunk && (IMG < 2 || c*256 + lane*4 < p.k)) *(float4v *) (p.x_out + (size_t) c*256 + lane*4) = xv[i];
             }
-        } else if (FIRST) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); __builtin_amdgcn_s_barrier(); }
-    } else
-    if (FIRST) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); __builtin_amdgcn_s_barrier(); }
+        } else { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); __builtin_amdgcn_s_barrier(); }
+    } else { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); __builtin_amdgcn_s_barrier(); }
 #ifdef MI_STAMPS
     {   // diagnostic builds: when are the activation loads back? (stamp 7 of the wave; the stamp waits for them, which the product does not do here)
         unsigned long long * stamps = p.stamps;
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        if (FIRST) { ST_STAMP(7); }
+        ST_STAMP(7);
     }
 #endif
     float scale = 1.0f;
@@ -668,8 +654,8 @@ static __device__ __forceinline__ void st_prologue_f32(const st_args & p, const 
 #pragma unroll
         for (int i = 0; i < NA; i++) if (wave + ST_NC*i < nchunk) ss += xv[i].x*xv[i].x + xv[i].y*xv[i].y + xv[i].z*xv[i].z + xv[i].w*xv[i].w;
         ss = wave_sum(ss);
-        if (lane == 0) L.red[wave] = ss;      // (everybody has read the previous phase's sums: three meetings lie in between)
-        st_consumers_meet(&L.sync[4], lane, n_norm++);
+        if (lane == 0) L.red[wave] = ss;
+        st_consumers_meet(&L.sync[4], lane);
         const float * red = L.red;
         ss = ((red[0] + red[1]) + (red[2] + red[3])) + ((red[4] + red[5]) + (red[6] + red[7]));
         scale = 1.0f/sqrtf(ss/(float) p.k + p.eps);
@@ -738,8 +724,8 @@ static __device__ __forceinline__ void st_prologue_f32(const st_args & p, const 
 // 16 quants as one 16-byte write, and every overhead instruction works for four blocks at once. Same arithmetic per element as quant_core.h's quant_frag_q8_K
 // (first element of largest magnitude, iscale = -127 / max, round to nearest even, min 127, d = 1 / iscale): the same bytes.
 //   quad q = blocks 4q .. 4q + 3; wave w owns quads w, w + 8, ...: NQ of them
-template <int NQ, bool FIRST, bool NORM>
-static __device__ __forceinline__ void st_prologue_q8k16(const st_args & p, const st_lds & L, int x_off, int seq, int & n_norm, int lane, int wave) {
+template <int NQ, bool NORM>
+static __device__ __forceinline__ void st_prologue_q8k16(const st_args & p, const st_lds & L, int x_off, int lane, int wave) {
     const int nchunk = p.nchunk;
     constexpr bool norm = NORM;      // (compile-time: as a run-time flag both forms were computed and selected between, square root and all)
     const int r = lane >> 4, l16 = lane & 15;
@@ -754,11 +740,11 @@ static __device__ __forceinline__ void st_prologue_q8k16(const st_args & p, cons
             wv[i][j] = norm ? *(const float4v *) (p.norm_w + (size_t) c*256 + l16*16 + 4*j) : float4v{ 1.0f, 1.0f, 1.0f, 1.0f };
         }
     }
-    if (FIRST) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); __builtin_amdgcn_s_barrier(); }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); __builtin_amdgcn_s_barrier();
 #ifdef MI_STAMPS
     {   unsigned long long * stamps = p.stamps;
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        if (FIRST) { ST_STAMP(7); }
+        ST_STAMP(7);
     }
 #endif
     float scale = 1.0f;
@@ -773,7 +759,7 @@ static __device__ __forceinline__ void st_prologue_q8k16(const st_args & p, cons
         }
         ss = wave_sum(ss);
         if (lane == 0) L.red[wave] = ss;
-        st_consumers_meet(&L.sync[4], lane, n_norm++);
+        st_consumers_meet(&L.sync[4], lane);
         const float * red = L.red;
         ss = ((red[0] + red[1]) + (red[2] + red[3])) + ((red[4] + red[5]) + (red[6] + red[7]));
         scale = 1.0f/sqrtf(ss/(float) p.k + p.eps);
@@ -810,7 +796,7 @@ static __device__ __forceinline__ void st_prologue_q8k16(const st_args & p, cons
         const float got = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(first << 2, __builtin_bit_cast(int, mx)));
         const float maxv = zero ? 1.0f : got;
 #ifdef MI_STAMPS
-        { unsigned long long * stamps = p.stamps; if (FIRST && i == 0) { asm volatile("" :: "v"(maxv)); ST_STAMP(8); } }
+        { unsigned long long * stamps = p.stamps; if (i == 0) { asm volatile("" :: "v"(maxv)); ST_STAMP(8); } }
 #endif
         const float iscale = -127.0f/maxv;
         // round to nearest even by the reference's own device (nearest_int: add 1.5 * 2^23, the integer sits in the low mantissa bits): the quant is the low BYTE of
@@ -832,7 +818,7 @@ static __device__ __forceinline__ void st_prologue_q8k16(const st_args & p, cons
         const float d = zero ? 0.0f : 1.0f/iscale;
         const int sum32 = sum + dpp_i<0xB1>(sum);       // (quad_perm [1,0,3,2]: the neighbour's 16-element sum)
 #ifdef MI_STAMPS
-        { unsigned long long * stamps = p.stamps; if (FIRST && i == 0) { asm volatile("" :: "v"(pk.x), "v"(sum32), "v"(d)); ST_STAMP(9); } }
+        { unsigned long long * stamps = p.stamps; if (i == 0) { asm volatile("" :: "v"(pk.x), "v"(sum32), "v"(d)); ST_STAMP(9); } }
 #endif
         if (c < nchunk) {
             char * ab = L.act + (size_t) c*ST_ACT_STRIDE;
@@ -847,12 +833,10 @@ static __device__ __forceinline__ void st_prologue_q8k16(const st_args & p, cons
     }
 }
 
-// ================= the consumers' share of one phase =================
-//   seq: how many phases this workgroup has run before (its LDS counters are cumulative); FIRST: the launch's first phase — the activation
-//   loads are queued before the loader starts (the barrier every wave of the workgroup takes exactly once)
-template <int TYPE, bool FIRST>
-static __device__ __forceinline__ void st_consumer_phase(const st_args & p, const st_group & g, int wg, int nwg, const st_lds & L, int slot0, int seq, int & n_norm,
-                                                         int lane, int wave, unsigned long long * stamps, int xt0 = 0, int xt1 = 0) {
+// ================= the consumers: image, stream, epilogue =================
+template <int TYPE>
+static __device__ __forceinline__ void st_consumers(const st_args & p, const st_group & g, int wg, int nwg, const st_lds & L,
+                                                    int lane, int wave, unsigned long long * stamps, int xt0 = 0, int xt1 = 0) {
     typedef st_unit<TYPE> U;
     const int nb = p.nb;
     const bool GLU = g.epi == EPI_GLU || g.neox2 > 0;      // two row streams
@@ -864,35 +848,35 @@ static __device__ __forceinline__ void st_consumer_phase(const st_args & p, cons
     uint32_t * sync = L.sync; char * act = L.act; float * dd = L.dd; float * part = L.part;
     const int ctid = threadIdx.x;                    // consumer thread id (the consumers are waves 0 .. ST_NC - 1)
 
-    // ---- the activation image (FIRST: the loads are requested before any weight is — a CU returns loads in request order) ----
+    // ---- the activation image (its loads are requested before any weight is — a CU returns loads in request order) ----
     const int mode = p.mode;
     constexpr int ST_IMG = TYPE == ST_MXFP4_B10 ? 3 : TYPE == ST_Q8_0_B10 ? 2 : (TYPE == T_Q8_0 || TYPE == T_Q4_0) ? 1 : 0;
-    if (mode == PRO_Q8) st_prologue_q8<FIRST>(p, L, ctid);
+    if (mode == PRO_Q8) st_prologue_q8(p, L, ctid);
     else if (ST_IMG == 0 && !p.planes && p.x && !(p.early & 0x100) && p.nchunk <= 128) {      // (bit 8 of `early`: GGML_MI355X_STREAM_Q16=0, the one-block-per-wave quantizer)
         if (mode == PRO_NORM) {
-            if (p.nchunk <= 32)      st_prologue_q8k16<1, FIRST, true>(p, L, g.x_off, seq, n_norm, lane, wave);
-            else if (p.nchunk <= 64) st_prologue_q8k16<2, FIRST, true>(p, L, g.x_off, seq, n_norm, lane, wave);
-            else                     st_prologue_q8k16<4, FIRST, true>(p, L, g.x_off, seq, n_norm, lane, wave);
+            if (p.nchunk <= 32)      st_prologue_q8k16<1, true>(p, L, g.x_off, lane, wave);
+            else if (p.nchunk <= 64) st_prologue_q8k16<2, true>(p, L, g.x_off, lane, wave);
+            else                     st_prologue_q8k16<4, true>(p, L, g.x_off, lane, wave);
         } else {
-            if (p.nchunk <= 32)      st_prologue_q8k16<1, FIRST, false>(p, L, g.x_off, seq, n_norm, lane, wave);
-            else if (p.nchunk <= 64) st_prologue_q8k16<2, FIRST, false>(p, L, g.x_off, seq, n_norm, lane, wave);
-            else                     st_prologue_q8k16<4, FIRST, false>(p, L, g.x_off, seq, n_norm, lane, wave);
+            if (p.nchunk <= 32)      st_prologue_q8k16<1, false>(p, L, g.x_off, lane, wave);
+            else if (p.nchunk <= 64) st_prologue_q8k16<2, false>(p, L, g.x_off, lane, wave);
+            else                     st_prologue_q8k16<4, false>(p, L, g.x_off, lane, wave);
         }
     }
     else if (mode == PRO_NORM) {
-        if (p.nchunk <= 8)        st_prologue_f32<1, FIRST, ST_IMG, true>(p, L, g.x_off, seq, n_norm, lane, wave);
-        else if (p.nchunk <= 16)  st_prologue_f32<2, FIRST, ST_IMG, true>(p, L, g.x_off, seq, n_norm, lane, wave);
-        else if (p.nchunk <= 32)  st_prologue_f32<4, FIRST, ST_IMG, true>(p, L, g.x_off, seq, n_norm, lane, wave);
-        else                      st_prologue_f32<8, FIRST, ST_IMG, true>(p, L, g.x_off, seq, n_norm, lane, wave);
+        if (p.nchunk <= 8)        st_prologue_f32<1, ST_IMG, true>(p, L, g.x_off, lane, wave);
+        else if (p.nchunk <= 16)  st_prologue_f32<2, ST_IMG, true>(p, L, g.x_off, lane, wave);
+        else if (p.nchunk <= 32)  st_prologue_f32<4, ST_IMG, true>(p, L, g.x_off, lane, wave);
+        else                      st_prologue_f32<8, ST_IMG, true>(p, L, g.x_off, lane, wave);
     } else {
-        if (p.nchunk <= 8)        st_prologue_f32<1, FIRST, ST_IMG, false>(p, L, g.x_off, seq, n_norm, lane, wave);
-        else if (p.nchunk <= 16)  st_prologue_f32<2, FIRST, ST_IMG, false>(p, L, g.x_off, seq, n_norm, lane, wave);
-        else if (p.nchunk <= 32)  st_prologue_f32<4, FIRST, ST_IMG, false>(p, L, g.x_off, seq, n_norm, lane, wave);
-        else                      st_prologue_f32<8, FIRST, ST_IMG, false>(p, L, g.x_off, seq, n_norm, lane, wave);
+        if (p.nchunk <= 8)        st_prologue_f32<1, ST_IMG, false>(p, L, g.x_off, lane, wave);
+        else if (p.nchunk <= 16)  st_prologue_f32<2, ST_IMG, false>(p, L, g.x_off, lane, wave);
+        else if (p.nchunk <= 32)  st_prologue_f32<4, ST_IMG, false>(p, L, g.x_off, lane, wave);
+        else                      st_prologue_f32<8, ST_IMG, false>(p, L, g.x_off, lane, wave);
     }
     ST_STAMP(1);
     asm volatile("s_waitcnt vmcnt(0)" :: "v"(xt0), "v"(xt1) : "memory");      // (the entry touches' registers are free from here on; nothing of this wave's is in flight any more)
-    st_consumers_meet(&sync[2], lane, seq);
+    st_consumers_meet(&sync[2], lane);
     ST_STAMP(2);
 
     // ---- the epilogue's operands of this thread's first row / pair: requested now, needed after the last slot ----
@@ -922,9 +906,8 @@ static __device__ __forceinline__ void st_consumer_phase(const st_args & p, cons
     // ---- the stream ----
     const uint32_t magic = p.magic;
     bool first = true;
-    int ring_i = (slot0 + wave) % S;
+    int ring_i = wave % S;
     for (int i = wave; i < nslots; i += ST_NC) {
-        const int gi = slot0 + i;
         const int si = GLU ? (i >= ns1) : 0, il = i - si*ns1;
         const int u = il*64 + lane;                              // unit inside the stream
         const bool live = u < n1;
@@ -932,12 +915,12 @@ static __device__ __forceinline__ void st_consumer_phase(const st_args & p, cons
         const int ib = nb == 1 ? 0 : uc - (int) __umulhi((uint32_t) uc, magic)*nb;      // (the magic number of nb = 1 does not fit 32 bits)
         const char * ab = act + (size_t) ib*(ST_IMG == 3 ? ST_ACT_STRIDE_FP4 : ST_IMG == 2 ? ST_ACT_STRIDE_B10 : ST_ACT_STRIDE);
         const float d8 = dd[ib];
-        st_wait_ge(&sync[0], (uint32_t)(gi + 1));
+        st_wait_ge(&sync[0], (uint32_t)(i + 1));
         if (first) { ST_STAMP(3); first = false; }
         const typename U::wfrag w = U::load(L.ring_a + (uint32_t) ring_i*L.slot_stride + (uint32_t)(live ? lane : 0)*U::UB);
         // the slot is free as soon as its bytes are in registers
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        if (lane == 0) st_flag_st(&sync[16 + ring_i], (uint32_t)(gi + 1));
+        if (lane == 0) st_flag_st(&sync[16 + ring_i], (uint32_t)(i + 1));
         ring_i += ST_NC; while (ring_i >= S) ring_i -= S;
         float res = U::dot(w, ab, d8);
         if (!live) res = 0.0f;
@@ -947,7 +930,7 @@ static __device__ __forceinline__ void st_consumer_phase(const st_args & p, cons
         } else if (live) part[(size_t) si*n1 + u] = res;
     }
     ST_STAMP(4);
-    st_consumers_meet(&sync[3], lane, 2*seq);
+    st_consumers_meet(&sync[3], lane);
     ST_STAMP(5);
 
     // ---- rows: partials added in a fixed order, epilogue with a lane per row (or rotation pair) ----
@@ -1004,7 +987,7 @@ static __device__ __forceinline__ void st_consumer_phase(const st_args & p, cons
     ST_STAMP(6);
 }
 
-// which group of the phase a workgroup belongs to
+// which group of the launch a workgroup belongs to
 static __device__ __forceinline__ int st_group_of(const st_args & p, int b, int & first, int & nwg) {
     int gi = 0;
 #pragma unroll
@@ -1017,14 +1000,15 @@ static __device__ __forceinline__ st_lds st_carve(char * lds, int nb_max, int np
     L.sync = (uint32_t *) lds;
     L.act = lds + 2*ST_SYNC_WORDS*4;
     L.dd = (float *) (L.act + (size_t) nb_max*act_stride);
-    L.red = L.dd + ((nb_max + 3) & ~3);              // [2][ST_NC] sums of squares (PRO_NORM)
+    L.red = L.dd + ((nb_max + 3) & ~3);              // the waves' sums of squares (PRO_NORM): ST_NC floats of the 16 kept here
     L.part = L.red + 16;
     L.ring_a = st_lds_addr((char *) (((size_t)(L.part + npart_max) + 15) & ~(size_t) 15));
     L.slot_stride = slot_stride; L.S = S;
     return L;
 }
 
-static __device__ __forceinline__ int st_phase_slots(const st_args & a, const st_group & g, int wg, int nwg) {
+// the slots a workgroup streams (st_loader_issue's count, for st_loader_drain. Written out at the call it compiles to other register numbers: kept a function)
+static __device__ __forceinline__ int st_nslots(const st_args & a, const st_group & g, int wg, int nwg) {
     int r0, R; st_rows(g, wg, nwg, r0, R);
     const int ns1 = (R*a.nb + 63) >> 6;
     return (g.epi == EPI_GLU || g.neox2 > 0) ? 2*ns1 : ns1;
@@ -1072,16 +1056,28 @@ __global__ void __launch_bounds__(ST_THREADS, 3) k_mmvq_stream(const st_args p) 
         if (g.eid) { asm volatile("s_waitcnt vmcnt(0)" : "+v"(e_raw) :: "memory"); __builtin_amdgcn_sched_barrier(0); }
         const int expert = __builtin_amdgcn_readfirstlane(e_raw);
         ST_STAMP(3);        // (loader: the expert index is here — or nothing was waited for)
-        st_loader_state ls = { 0, 0, 0, 0, 0, 0, 0, 0 };
-        if (is_a) st_loader_phase<TA, NT>(p, g, wg, nwg, L, 0, ls, lane, expert, early);
-        else      st_loader_phase<TB, NT>(p, g, wg, nwg, L, 0, ls, lane, expert, early);
-        st_loader_drain(L, st_phase_slots(p, g, wg, nwg), ls, lane);
+        st_loader_state ls = {};
+        if (is_a) st_loader_issue<TA, NT>(p, g, wg, nwg, L, ls, lane, expert, early);
+        else      st_loader_issue<TB, NT>(p, g, wg, nwg, L, ls, lane, expert, early);
+        st_loader_drain(L, st_nslots(p, g, wg, nwg), ls, lane);
         ST_STAMP(1);
         return;
     }
-    int n_norm = 0;
-    if (is_a) st_consumer_phase<TA, true>(p, g, wg, nwg, L, 0, 0, n_norm, lane, wave, stamps, xt0, xt1);
-    else      st_consumer_phase<TB, true>(p, g, wg, nwg, L, 0, 0, n_norm, lane, wave, stamps, xt0, xt1);
+    if (is_a) st_consumers<TA>(p, g, wg, nwg, L, lane, wave, stamps, xt0, xt1);
+    else      st_consumers<TB>(p, g, wg, nwg, L, lane, wave, stamps, xt0, xt1);
 }
+
+// ---- host side (mmvq_stream.hip) ----
+// One grouped launch, planned ONCE: whether the streamed kernel takes it (ok) and, if it does, everything its launch needs. The admission tests,
+// the share of workgroups per group and the size of the slot ring are all decided in mul_mat_vec_q_stream_plan; the launcher only launches.
+struct st_plan {
+    bool ok;
+    st_args a;                 // filled, a.S included
+    int blocks, S; size_t lds;
+    int ta, tb; bool glu;      // the instantiation k_mmvq_stream<ta, tb, true, glu>: the unit types (ta <= tb) of a pair that has a kernel
+    double bytes_total;        // weight bytes the launch streams
+};
+st_plan mul_mat_vec_q_stream_plan(const mmvq_group * groups, int n_groups, int64_t k, const mmvq_input & in, const mmvq_rope * rope);
+void mul_mat_vec_q_stream(const st_plan & plan, hipStream_t stream, mmvq_launch_rec * rec = nullptr);      // plan.ok only
 
 } // namespace mi355x

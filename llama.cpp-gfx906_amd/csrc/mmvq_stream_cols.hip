@@ -55,8 +55,8 @@ __global__ void __launch_bounds__(ST_THREADS, 1) k_mmvq_stream_cols(const st_arg
     if (wave == ST_NC) {
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
-        st_loader_state ls = { 0, 0, 0, 0, 0, 0, 0 };
-        st_loader_phase<TYPE, NT>(p, g, wg, nwg, L, 0, ls, lane, 0);
+        st_loader_state ls = {};
+        st_loader_issue<TYPE, NT>(p, g, wg, nwg, L, ls, lane, 0);
         st_loader_drain(L, nslots, ls, lane);
         return;
     }
@@ -107,7 +107,7 @@ __global__ void __launch_bounds__(ST_THREADS, 1) k_mmvq_stream_cols(const st_arg
             L.dd[(size_t) col*c.nbp + ib] = dv;
         }
     }
-    st_consumers_meet(&L.sync[2], lane, 0);
+    st_consumers_meet(&L.sync[2], lane);
 
     // ---- the stream: a lane owns one unit of the slot and multiplies it with every column ----
     const bool row16 = (nb & 15) == 0;
@@ -137,7 +137,7 @@ __global__ void __launch_bounds__(ST_THREADS, 1) k_mmvq_stream_cols(const st_arg
             if ((lane & ((1 << gsh) - 1)) == 0 && live) L.part[(size_t) col*c.npc + (u >> gsh)] = res;
         }
     }
-    st_consumers_meet(&L.sync[3], lane, 0);
+    st_consumers_meet(&L.sync[3], lane);
 
     // ---- (row, column): partials added in a fixed order ----
     for (int e = ctid; e < R*c.n; e += ST_NC*64) {
@@ -146,19 +146,9 @@ __global__ void __launch_bounds__(ST_THREADS, 1) k_mmvq_stream_cols(const st_arg
     }
 }
 
-static int stc_cu_count() {
-    static int n_cu = 0;
-    if (n_cu == 0) {
-        int dev = 0; hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) n_cu = prop.multiProcessorCount;
-        if (n_cu <= 0) n_cu = 256;
-    }
-    return n_cu;
-}
-
 template <int TYPE, int N>
 static void stc_launch(const st_args & a, const st_cols & c, int blocks, size_t lds, hipStream_t stream) {
-    MI_LDS_LIMIT_OR_DIE(163840, k_mmvq_stream_cols<TYPE, N, true>);
+    MI_LDS_LIMIT_OR_DIE(MI_LDS_BUDGET, k_mmvq_stream_cols<TYPE, N, true>);
     hipLaunchKernelGGL((k_mmvq_stream_cols<TYPE, N, true>), dim3((unsigned) blocks), dim3(ST_THREADS), lds, stream, a, c);
 }
 
@@ -184,7 +174,7 @@ bool mul_mat_vec_q_stream_cols(int type_a, const void * W, size_t w_row_stride, 
     s.ralign = 1;
     while (((int64_t) s.ralign*nb*ub) % 16 != 0) s.ralign *= 2;
     const int nru = std::max(1, (int)(m/s.ralign));
-    const int blocks = std::min(stc_cu_count(), nru);
+    const int blocks = std::min(device_cu_count(), nru);
     a.block_end[0] = blocks;
     const int Rmax = ((nru + blocks - 1)/blocks)*s.ralign + (int)(m - (m/s.ralign)*s.ralign);
     st_cols c = {};
@@ -199,8 +189,8 @@ bool mul_mat_vec_q_stream_cols(int type_a, const void * W, size_t w_row_stride, 
     const size_t fixed = 2*ST_SYNC_WORDS*4 + (size_t) n*c.col_stride + (size_t) n*c.nbp*4 + (size_t) N*c.npc*4 + 16;
     const int slot = ((64*ub + 1023)/1024)*1024;
     const int nslots_max = (int)(((int64_t) Rmax*nb + 63)/64);
-    if (fixed + (size_t) std::min(nslots_max, 2)*slot > 163840) return false;
-    int S = (int)((163840 - (int64_t) fixed)/slot);
+    if (fixed + (size_t) std::min(nslots_max, 2)*slot > (size_t) MI_LDS_BUDGET) return false;
+    int S = (int)((MI_LDS_BUDGET - (int64_t) fixed)/slot);
     if (S > nslots_max) S = nslots_max;
     if (S > ST_MAX_RING) S = ST_MAX_RING;
     a.S = S;
