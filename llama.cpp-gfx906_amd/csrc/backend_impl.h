@@ -94,8 +94,11 @@ struct mi_pass {
     // the activations of a quantized mat-mul as the scratch holds them (quantized, or the bf16 copy the MFMA prefill kernel reads); off: where in the
     // scratch the bf16 copy sits (a producer kernel that still reads offset 0 writes its result's copy higher up). Nodes lo..hi are the launch that
     // produced it (empty when a node quantized its own input): their writes over `data` do not end it, anybody else's do.
+    // Rows r of the input: data + (r % n_inner)*s_inner + (r / n_inner)*s_outer. Written and looked up through the operations below only.
     struct { const void * data; int64_t k, n_inner, n_outer; size_t s_inner, s_outer; int kind; act_q8 q; bool valid; size_t span;
              size_t off; int lo = 0, hi = -1; } aq = {};
+    static constexpr int ACT_KIND_BF16 = -16;          // aq.kind of the dense bf16 copy the MFMA prefill kernel reads
+    static constexpr size_t NO_ACT = ~(size_t) 0;
     // the last router launch: it ranked `vals` (probabilities, or logits) into `sorted` and left the eight best values in rank order at moe_ws + 64
     // (floats the kernel does not use otherwise): a combine that gathers vals[sorted[u]] takes them from there — one load instead of two dependent cold ones.
     // Keyed on addresses, so any later node that writes over vals or sorted (an allocator reuses a dead router's memory for the next layer's, whose router
@@ -118,6 +121,36 @@ struct mi_pass {
     void abandon() { aq.valid = false; pp.active = false; }            // a pass unwound by an error
     void drop_act() { aq.valid = false; }                              // a launch reuses the scratch
     void note_writes(const struct ggml_cgraph * g, int i, int n);      // nodes [i, i+n) have run: what they wrote over ends aq / rt
+
+    // look-ups: does the scratch hold the image of exactly this input? Each asks for what its caller relies on, no more.
+    // the bf16 copy of n rows of k floats, row_stride bytes apart: its offset in the scratch, or NO_ACT (a caller that needs it at the start asks `== 0`)
+    size_t bf16_at(const void * x, int64_t k, int64_t n, size_t row_stride) const {
+        return aq.valid && aq.kind == ACT_KIND_BF16 && aq.data == x && aq.k == k && aq.n_inner == n && aq.s_inner == row_stride ? aq.off : NO_ACT;
+    }
+    // the quantized image of these rows in this format, or NULL
+    const act_q8 * q8_of(const void * x, int64_t k, int64_t n_inner, int64_t n_outer, size_t s_inner, size_t s_outer, int kind) const {
+        return aq.valid && aq.data == x && aq.k == k && aq.n_inner == n_inner && aq.n_outer == n_outer && aq.s_inner == s_inner && aq.s_outer == s_outer &&
+               aq.kind == kind ? &aq.q : nullptr;
+    }
+    // ... of one row (no stride to compare)
+    const act_q8 * q8_of_row(const void * x, int64_t k, int kind) const {
+        return aq.valid && aq.data == x && aq.k == k && aq.n_inner == 1 && aq.n_outer == 1 && aq.kind == kind ? &aq.q : nullptr;
+    }
+    bool holds_image_of(const void * x) const { return aq.valid && aq.data == x; }      // any image, any format
+    size_t act_off() const { return aq.valid ? aq.off : 0; }                             // where the live image starts (0 when there is none)
+
+    // writes. converted_*: a node made the image of its own input (at the start of the scratch); produced_*: the launch that covers nodes lo..hi
+    // left the image of its result (bf16: at offset off)
+    void converted_q8(const void * x, int64_t k, int64_t n_inner, int64_t n_outer, size_t s_inner, size_t s_outer, int kind, const act_q8 & q) {
+        aq = { x, k, n_inner, n_outer, s_inner, s_outer, kind, q, true, (size_t)(n_outer - 1)*s_outer + (size_t)(n_inner - 1)*s_inner + (size_t) k*4, 0, 0, -1 };
+    }
+    void produced_q8(int lo, int hi, const void * x, int64_t k, int64_t n, size_t row_stride, int kind, const act_q8 & q) {
+        converted_q8(x, k, n, 1, row_stride, 0, kind, q); aq.lo = lo; aq.hi = hi;
+    }
+    void converted_bf16(const void * x, int64_t k, int64_t n, size_t row_stride) { converted_q8(x, k, n, 1, row_stride, 0, ACT_KIND_BF16, act_q8{}); }
+    void produced_bf16(int lo, int hi, const void * x, int64_t k, int64_t n, size_t row_stride, size_t off) {
+        converted_bf16(x, k, n, row_stride); aq.off = off; aq.lo = lo; aq.hi = hi;
+    }
 };
 
 struct mi_backend_ctx {

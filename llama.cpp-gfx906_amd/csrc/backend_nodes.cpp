@@ -37,7 +37,7 @@ static void pp_flush(mi_backend_ctx * c) {
 
 void pass_end(mi_backend_ctx * c) {
     pp_flush(c);
-    c->pass.aq.valid = false;
+    c->pass.drop_act();
 }
 
 // FLASH_ATTN_EXT: the dense f16 copies its kernels need — the V cache transposed for the matrix-core prefill kernel (always: rows over cells are what it
@@ -52,20 +52,16 @@ void fa_kv16_plan(const struct ggml_tensor * n, size_t & k_bytes, size_t & v_byt
 
 // quantize (or reuse) the activations of a quantized mat-mul: rows r -> x + (r % n_inner)*s_inner + (r / n_inner)*s_outer
 static act_q8 get_act(mi_backend_ctx * c, const void * x, int64_t k, int64_t n_inner, int64_t n_outer, size_t s_inner, size_t s_outer, int kind) {
-    if (c->pass.aq.valid && c->pass.aq.data == x && c->pass.aq.k == k && c->pass.aq.n_inner == n_inner && c->pass.aq.n_outer == n_outer &&
-        c->pass.aq.s_inner == s_inner && c->pass.aq.s_outer == s_outer && c->pass.aq.kind == kind) {
+    if (const act_q8 * have = c->pass.q8_of(x, k, n_inner, n_outer, s_inner, s_outer, kind)) {
         c->cnt.act_quant_reused++;
-        return c->pass.aq.q;
+        return *have;
     }
     act_q8 q = act_q8_carve(c->scratch, kind, k, n_inner*n_outer);
     quantize_act((const float *) x, n_inner, s_inner, s_outer, q, c->stream);
     c->cnt.act_quant_launches++; c->cnt.kernels_launched++;
-    c->pass.aq = { x, k, n_inner, n_outer, s_inner, s_outer, kind, q, true,
-              (size_t)(n_outer - 1)*s_outer + (size_t)(n_inner - 1)*s_inner + (size_t) k*4 };
+    c->pass.converted_q8(x, k, n_inner, n_outer, s_inner, s_outer, kind, q);
     return q;
 }
-
-static constexpr int ACT_KIND_BF16 = -16;   // aq.kind of the dense bf16 copy the MFMA prefill kernel reads
 
 // F16 activations of a quantized mat-mul (tests/test-backend-ops.cpp:5715-5716): a dense F32 copy in c->cvt first (the CPU backend converts src1 to the
 // weights' vec_dot type row by row as well), then the F32 path reads `tmp`, the copy's descriptor
@@ -110,14 +106,16 @@ static void op_mul_mat(mi_backend_ctx * c, struct ggml_tensor * dst, struct ggml
                     c->cnt.mmvq_launches++;
                 } else {
                     // the scratch holds the bf16 copy of the activations; wq/wk/wv and gate/up read the same ones: convert once
-                    const bool ready = c->pass.aq.valid && c->pass.aq.kind == ACT_KIND_BF16 && c->pass.aq.data == bp && c->pass.aq.k == K && c->pass.aq.n_inner == N &&
-                                       c->pass.aq.s_inner == b->nb[1];
-                    void * scr = (char *) c->scratch + (ready ? c->pass.aq.off : 0);
+                    const size_t at = c->pass.bf16_at(bp, K, N, b->nb[1]);      // (at any offset: a producer may have left it above its own)
+                    const bool ready = at != mi_pass::NO_ACT;
+                    const size_t off = ready ? at : 0;
+                    void * scr = (char *) c->scratch + off;
                     if (out) mul_mat_q((int) a->type, W, a->nb[1], M, K, (const float *) bp, b->nb[1], N, scr, ready, (float *) out->data, out->nb[1],
                                        (const float *) res->data, res->ne[1] == 1 && N > 1 ? 0 : res->nb[1], c->stream, defer);     // (a bias row: the same addend for every token)
                     else     mul_mat_q((int) a->type, W, a->nb[1], M, K, (const float *) bp, b->nb[1], N, scr, ready, d, dst->nb[1], nullptr, 0, c->stream);
                     if (ready) c->cnt.act_quant_reused++;
-                    else c->pass.aq = { bp, K, N, 1, b->nb[1], 0, ACT_KIND_BF16, act_q8{}, true, (size_t)(N - 1)*b->nb[1] + (size_t) K*4 };
+                    else c->pass.converted_bf16(bp, K, N, b->nb[1]);
+                    if (defer) defer->planes_off += off;      // (mul_mat_q counted from `scr`; now from the start of the scratch)
                     c->cnt.mmq_launches++; c->cnt.kernels_launched += ready ? 0 : 1;
                 }
                 prof_end(c);
@@ -428,7 +426,7 @@ static int try_fused_mmv(mi_backend_ctx * c, struct ggml_cgraph * g, int i, int 
         if (act_kind_for((int) m->src[0]->type) != kind) {
             // another activation format (Mixtral: wq Q4_K, wk / wv Q8_0) joins only a launch in which every workgroup quantizes the activation
             // itself: the norm prologue, or the plain quantizing one when no image of b is cached
-            const bool cached_b = c->pass.aq.valid && c->pass.aq.data == b->data;
+            const bool cached_b = c->pass.holds_image_of(b->data);
             if (!(norm || !cached_b) || !mul_mat_vec_q_fused_can_group_mixed(chains[0].grp.type, (int) m->src[0]->type) ||
                 !mul_mat_vec_q_fused_prologue_supported(n->src[0]->ne[0], kind) || !mul_mat_vec_q_fused_prologue_supported(n->src[0]->ne[0], act_kind_for((int) m->src[0]->type))) break;
         }
@@ -513,7 +511,7 @@ static int try_fused_mmv(mi_backend_ctx * c, struct ggml_cgraph * g, int i, int 
     const int64_t K = n->src[0]->ne[0];
     mmvq_input in = {};
     in.act_kind = kind;
-    const bool cached = c->pass.aq.valid && c->pass.aq.data == b->data && c->pass.aq.k == K && c->pass.aq.n_inner == 1 && c->pass.aq.n_outer == 1 && c->pass.aq.kind == kind;
+    const act_q8 * cached = c->pass.q8_of_row(b->data, K, kind);
     // The norm's product is left unwritten only where nobody else can look at it: not when the view handed to graph_compute ENDS at one of
     // its consumers (the scheduler's eval-callback cuts the graph there and the callback — tools/imatrix/imatrix.cpp:223-247 — reads the mat-mul's
     // src1), and not for result_norm, which llama_context reads back as the embeddings without an OUTPUT flag (src/llama-context.cpp:1137-1151)
@@ -525,7 +523,7 @@ static int try_fused_mmv(mi_backend_ctx * c, struct ggml_cgraph * g, int i, int 
     } else if (norm) {
         return -1;      // the caller runs the norm (+ quantization) as its own kernel, then comes back without `norm`
     } else if (cached) {
-        in.mode = PRO_Q8; in.act = c->pass.aq.q; c->cnt.act_quant_reused++;
+        in.mode = PRO_Q8; in.act = *cached; c->cnt.act_quant_reused++;
     } else if (mul_mat_vec_q_fused_prologue_supported(K, kind)) {
         in.mode = PRO_QUANT; in.x = (const float *) b->data;
     } else {
@@ -580,9 +578,7 @@ static int try_fused_mmv(mi_backend_ctx * c, struct ggml_cgraph * g, int i, int 
         }
     }
     emit_mmv(c, grp, nc, K, in, rope, fin_t ? &fin : nullptr, wbytes);
-    if (fin_t) {
-        c->pass.aq = { fin_t->data, grp[0].m, 1, 1, fin_t->nb[1], 0, fin.kind, fin_q, true, (size_t) grp[0].m*4, 0, from, last };
-    }
+    if (fin_t) c->pass.produced_q8(from, last, fin_t->data, grp[0].m, 1, fin_t->nb[1], fin.kind, fin_q);
     for (int r = 0; r < n_def; r++) compute_node(c, g, deferred[r]);
     return last;
 }
@@ -658,9 +654,7 @@ static int try_fused_attn(mi_backend_ctx * c, struct ggml_cgraph * g, int i) {
                      mask ? mask->data : nullptr, mask ? mask->nb[1] : 0, mask && mask->type == GGML_TYPE_F16,
                      sm->src[2] ? (const float *) sm->src[2]->data : nullptr, y16 ? nullptr : (float *) ct->data, (size_t) hd*n_head*4,
                      hd, n_kv, n_head, n_head_kv, T, op_f32(sm, 0), c->stream, true, y16 ? (uint16_t *) c->scratch : nullptr);
-        if (y16) {
-            c->pass.aq = { ct->data, hd*n_head, T, 1, ct->nb[1], 0, ACT_KIND_BF16, act_q8{}, true, (size_t)(T - 1)*ct->nb[1] + (size_t) hd*n_head*4, 0, i, j3 };
-        }
+        if (y16) c->pass.produced_bf16(i, j3, ct->data, hd*n_head, T, ct->nb[1], 0);
         c->cnt.kernels_launched++;
         return j3 - i + 1;
     }
@@ -1120,7 +1114,7 @@ static int try_fused_prefill_glu(mi_backend_ctx * c, struct ggml_cgraph * g, int
         !ggml_is_contiguous(gl) || !((gl->src[0] == nx && gl->src[1] == n) || (gl->src[0] == n && gl->src[1] == nx))) return 0;
     const int64_t K = a->ne[0], M = a->ne[1], N = b->ne[1];
     if (mul_mat_q_scratch_bytes(K, N, M) > c->scratch_size) return 0;
-    const bool ready = c->pass.aq.valid && c->pass.aq.kind == ACT_KIND_BF16 && c->pass.aq.data == b->data && c->pass.aq.k == K && c->pass.aq.n_inner == N && c->pass.aq.s_inner == b->nb[1] && c->pass.aq.off == 0;
+    const bool ready = c->pass.bf16_at(b->data, K, N, b->nb[1]) == 0;      // (at the start only: this launch reads its activations there)
     // ffn_down reads the result next: the kernel writes its bf16 copy (above this kernel's own activation copy) instead of the f32 tensor
     const struct ggml_tensor * down = prefill_mm_consumer(c, g, j2, gl);
     const size_t off2 = mul_mat_q_x_bytes(K, N);
@@ -1130,9 +1124,8 @@ static int try_fused_prefill_glu(mi_backend_ctx * c, struct ggml_cgraph * g, int
                   c->scratch, ready, y16 ? nullptr : (float *) gl->data, gl->nb[1], c->stream, y16 ? (uint16_t *) ((char *) c->scratch + off2) : nullptr);
     prof_end(c);
     if (ready) c->cnt.act_quant_reused++;
-    if (y16) {
-        c->pass.aq = { gl->data, M, N, 1, gl->nb[1], 0, ACT_KIND_BF16, act_q8{}, true, (size_t)(N - 1)*gl->nb[1] + (size_t) M*4, off2, i, j2 };
-    } else if (!ready) c->pass.aq = { b->data, K, N, 1, b->nb[1], 0, ACT_KIND_BF16, act_q8{}, true, (size_t)(N - 1)*b->nb[1] + (size_t) K*4 };
+    if (y16) c->pass.produced_bf16(i, j2, gl->data, M, N, gl->nb[1], off2);
+    else if (!ready) c->pass.converted_bf16(b->data, K, N, b->nb[1]);
     c->cnt.mmq_launches++; c->cnt.kernels_launched += ready ? 1 : 2;
     c->cnt.weight_bytes += (uint64_t) 2*M*ggml_row_size(a->type, K);
     return j2 - i + 1;
@@ -1207,7 +1200,7 @@ static int try_fused_prefill_qkv(mi_backend_ctx * c, struct ggml_cgraph * g, int
         wbytes += (uint64_t) a->ne[1]*ggml_row_size(a->type, a->ne[0]);
     }
     const int64_t K = b->ne[0], N = b->ne[1];
-    const bool ready = c->pass.aq.valid && c->pass.aq.kind == ACT_KIND_BF16 && c->pass.aq.data == b->data && c->pass.aq.k == K && c->pass.aq.n_inner == N && c->pass.aq.s_inner == b->nb[1] && c->pass.aq.off == 0;
+    const bool ready = c->pass.bf16_at(b->data, K, N, b->nb[1]) == 0;      // (at the start only: this launch reads its activations there)
     prof_begin(c, types[0], m[0] + m[1] + (nc > 2 ? m[2] : 0), K, N, wbytes);
     // the KV-cache writes that follow (SET_ROWS of rope(k) as f16 rows, SET_ROWS of v as an element scatter into the transposed cache — the pair
     // try_fused_kv_store takes) ride on the same combine pass
@@ -1249,7 +1242,7 @@ static int try_fused_prefill_qkv(mi_backend_ctx * c, struct ggml_cgraph * g, int
     if (biased && mul_mat_q_multi(nc, types, W, wrs, m, bdst, bdstride, K, (const float *) b->data, b->nb[1], N, c->scratch, c->scratch_size, ready, nullptr, nullptr, nullptr, c->stream, seg_bias)) {
         prof_end(c);
         if (ready) c->cnt.act_quant_reused++;
-        else c->pass.aq = { b->data, K, N, 1, b->nb[1], 0, ACT_KIND_BF16, act_q8{}, true, (size_t)(N - 1)*b->nb[1] + (size_t) K*4 };
+        else c->pass.converted_bf16(b->data, K, N, b->nb[1]);
         c->cnt.mmq_launches++; c->cnt.kernels_launched += ready ? 1 : 2; c->cnt.weight_bytes += wbytes;
         for (int q = 0; q < nc; q++) if (ch[q].rope >= 0) compute_node(c, g, ch[q].rope);
         return ch[nc - 1].end - i + 1;
@@ -1264,7 +1257,7 @@ static int try_fused_prefill_qkv(mi_backend_ctx * c, struct ggml_cgraph * g, int
     prof_end(c);
     if (!done) { if (c->profiling && !c->prof_suspend) c->prof.pop_back(); return 0; }
     if (ready) c->cnt.act_quant_reused++;
-    else c->pass.aq = { b->data, K, N, 1, b->nb[1], 0, ACT_KIND_BF16, act_q8{}, true, (size_t)(N - 1)*b->nb[1] + (size_t) K*4 };
+    else c->pass.converted_bf16(b->data, K, N, b->nb[1]);
     c->cnt.mmq_launches++; c->cnt.kernels_launched += ready ? 1 : 2; c->cnt.weight_bytes += wbytes;
     for (int q = 0; q < nc; q++) {
         if (ch[q].add >= 0) compute_node(c, g, ch[q].add);
@@ -1302,7 +1295,7 @@ static int try_fused_prefill_add(mi_backend_ctx * c, struct ggml_cgraph * g, int
                         nrm->ne[2] == 1 && nrm->ne[3] == 1;
         if (!ok) { nrm = nullptr; mul = nullptr; }
     }
-    mmq_deferred df = { 0, nullptr };
+    mmq_deferred df = {};
     op_mul_mat(c, n, nx, other, nrm ? &df : nullptr);
     if (!nrm || df.np == 0) return j - i + 1;          // no k split: the epilogue has added the residual; the norm runs as usual
     const int64_t M = n->ne[0], N = n->ne[1];
@@ -1312,13 +1305,13 @@ static int try_fused_prefill_add(mi_backend_ctx * c, struct ggml_cgraph * g, int
     const struct ggml_tensor * mm = jm > 0 ? g->nodes[jm] : nullptr;
     uint16_t * y16 = nullptr;
     if (mm && mm->op == GGML_OP_MUL_MAT && mm->src[1] == mul && ggml_is_quantized(mm->src[0]->type) && N > MMVQ_MAX_N && mul->ne[2] == 1 && mul->ne[3] == 1 &&
-        (const char *) c->scratch + (c->pass.aq.valid ? c->pass.aq.off : 0) + mul_mat_q_x_bytes(M, N) <= (const char *) df.planes) {
+        c->pass.act_off() + mul_mat_q_x_bytes(M, N) <= df.planes_off) {
         y16 = (uint16_t *) c->scratch;
     }
     combine_rms_norm(df.planes, df.np, M, N, (const float *) other->data, other->nb[1], (float *) nx->data, nx->nb[1], (const float *) w->data,
                      (float *) mul->data, mul->nb[1], y16, op_f32(nrm, 0), c->stream);
     c->cnt.kernels_launched++;
-    if (y16) c->pass.aq = { mul->data, M, N, 1, mul->nb[1], 0, ACT_KIND_BF16, act_q8{}, true, (size_t)(N - 1)*mul->nb[1] + (size_t) M*4, 0, i, jn + 1 };
+    if (y16) c->pass.produced_bf16(i, jn + 1, mul->data, M, N, mul->nb[1], 0);
     else c->pass.drop_act();
     return jn + 1 - i + 1;
 }
@@ -1365,8 +1358,7 @@ static int try_fused_norm(mi_backend_ctx * c, struct ggml_cgraph * g, int i) {
         const act_q8 q = act_q8_carve(c->scratch, kind, node->ne[0], node->ne[1]);
         rms_norm_mul_quant((const float *) s0->data, s0->nb[1], (const float *) w->data, (float *) mul->data, mul->nb[1], q,
                            node->ne[0], node->ne[1], op_f32(node, 0), c->stream);
-        c->pass.aq = { mul->data, node->ne[0], node->ne[1], 1, mul->nb[1], 0, kind, q, true,
-                       (size_t)(node->ne[1] - 1)*mul->nb[1] + (size_t) node->ne[0]*4, 0, i, i + 1 };
+        c->pass.produced_q8(i, i + 1, mul->data, node->ne[0], node->ne[1], mul->nb[1], kind, q);
         c->cnt.kernels_launched++; c->cnt.act_quant_launches++;
         return 2;
     }
@@ -1378,7 +1370,7 @@ static int try_fused_norm(mi_backend_ctx * c, struct ggml_cgraph * g, int i) {
         y16 = (uint16_t *) c->scratch;
     }
     rms_norm_mul(desc(s0), desc(w), nullptr, desc(mul), op_f32(node, 0), c->stream, y16);
-    if (y16) c->pass.aq = { mul->data, mul->ne[0], mul->ne[1], 1, mul->nb[1], 0, ACT_KIND_BF16, act_q8{}, true, (size_t)(mul->ne[1] - 1)*mul->nb[1] + (size_t) mul->ne[0]*4, 0, i, i + 1 };
+    if (y16) c->pass.produced_bf16(i, i + 1, mul->data, mul->ne[0], mul->ne[1], mul->nb[1], 0);
     c->cnt.kernels_launched++;
     return 2;
 }

@@ -68,16 +68,22 @@ void mul_mat_vec_q_id(int type_a, const void * W, size_t w_row_stride, size_t w_
                       float * dst, size_t dst_nb1, size_t dst_nb2, hipStream_t stream);
 
 // ---- quantized mat-mat (prefill, n > MMVQ_MAX_N): dequantize-to-bf16 tiles in LDS + v_mfma_f32_32x32x16_bf16 ----
+// Host side (mmq.hip): every launch form asks a pure plan function (mmq_plan_one / _multi / _glu: tile size, k split, grid, 16-wave kernel or not) and
+// mul_mat_q_layout for where things sit in the scratch, then only sets pointers and launches.
 // x: f32 rows of k floats at x + i*x_row_stride; scratch: mul_mat_q_scratch_bytes(k, n, m) bytes (the bf16 copy of x + the split-K planes)
 // (scratch_ready: it already holds the copy of exactly this x — the caller's cache — so the conversion pass is skipped)
 // res != NULL: dst = W.x + res (f32 rows of m floats at res + i*res_row_stride; may be dst itself) — the residual ADD of build_attn / build_ffn
-size_t mul_mat_q_scratch_bytes(int64_t k, int64_t n, int64_t m);
+// the scratch of one launch: the bf16 copy of x in [0, x_end), n_planes split-k planes (dense [n][m] f32 each) from planes_off; total includes the slack
+// behind them. A producer kernel that writes the next mat-mul's copy while this one's is still read puts it at x_end as well.
+struct mmq_layout { size_t x_end, planes_off, planes_bytes, total; };
+mmq_layout mul_mat_q_layout(int64_t k, int64_t n, int64_t m, int n_planes = 4);
+size_t mul_mat_q_scratch_bytes(int64_t k, int64_t n, int64_t m);     // = layout(k, n, m).total
 void mul_mat_q(int type_a, const void * W, size_t w_row_stride, int64_t m, int64_t k,
                const float * x, size_t x_row_stride, int64_t n, void * scratch, bool scratch_ready, float * dst, size_t dst_col_stride_bytes,
                const float * res, size_t res_row_stride, hipStream_t stream, struct mmq_deferred * defer = nullptr);
 // defer != NULL: when the launch splits k, the pass that adds the planes (and res) is left to the caller (who fuses it with the norm that
-// follows): np = number of planes (0: nothing deferred, dst is complete), planes = dense [np][n][m] f32 in the scratch
-struct mmq_deferred { int np; const float * planes; };
+// follows): np = number of planes (0: nothing deferred, dst is complete), planes = dense [np][n][m] f32 in the scratch, planes_off bytes behind `scratch`
+struct mmq_deferred { int np; const float * planes; size_t planes_off; };
 
 struct mmvq_rope;
 // KV-cache writes done by the pass that combines the launch's split-k planes: per segment, mode 0 none | 1 f16 rows st16[idx[token]*st_row_elems + col] |
@@ -96,7 +102,7 @@ bool mul_mat_q_glu_supported(int64_t m, int64_t n);
 void mul_mat_q_glu(int type_a, const void * Wg, const void * Wu, size_t w_row_stride, int64_t m, int64_t k,
                    const float * x, size_t x_row_stride, int64_t n, void * scratch, bool scratch_ready, float * dst, size_t dst_col_stride_bytes, hipStream_t stream,
                    uint16_t * y16 = nullptr);
-size_t mul_mat_q_x_bytes(int64_t k, int64_t n);      // size of the bf16 activation copy at the start of the scratch
+size_t mul_mat_q_x_bytes(int64_t k, int64_t n);      // size of the bf16 activation copy at the start of the scratch (= layout(k, n, 0).x_end)
 
 // ---- MUL_MAT_ID for many tokens (src/llama-graph.cpp:569-595): (token, slot) pairs sorted by expert on the device, then the tiled
 // MFMA kernel per (expert, 128 pairs). b: f32 [k, n_b, n_tokens] (n_b = 1 or n_used); ids: i32 [n_used, n_tokens] (strided);

@@ -993,28 +993,120 @@ __global__ void __launch_bounds__(768) __attribute__((amdgpu_waves_per_eu(3, 3))
 constexpr size_t MQ_LDS_BYTES_WS256 = 2*((size_t) 256*MQ_LD + MQ_WS_XTILE);
 static bool mmq_ws_on() { static const bool on = env_on("GGML_MI355X_MMQ_WS"); return on; }
 static bool mmq_w16_on() { static const bool on = env_on("GGML_MI355X_MMQ16"); return on; }
-
 constexpr size_t MQ_LDS_BYTES = 4*(size_t) MQ_BM*MQ_LD;
-constexpr size_t MQ_LDS_BYTES_256 = 2*(size_t)(MQ_BM + 256)*MQ_LD;
+constexpr size_t MQ_LDS_BYTES_256 = 2*(size_t)(MQ_BM + 256)*MQ_LD;          // 108 KB of dynamic LDS: more than the 64 KB a kernel gets without asking
 constexpr size_t MQ_LDS_BYTES_DUAL = 2*(size_t)(2*MQ_BM + 256)*MQ_LD;
-
-// 108 KB of dynamic LDS: more than the 64 KB a kernel gets without asking
-template <int T_>
-static void launch_mmq_wide(dim3 grid, const mmq_args & a, hipStream_t stream) {
-    MI_LDS_LIMIT_OR_DIE(MQ_LDS_BYTES_256, k_mmq<T_, 256>);
-    const bool w16 = mmq_w16_on();
-    if (w16 && !a.moe && a.ne12 == 1 && a.r2 == 1 && a.r3 == 1) {
-        MI_LDS_LIMIT_OR_DIE(MQ_LDS_BYTES_256, k_mmq16<T_>);
-        hipLaunchKernelGGL((k_mmq16<T_>), grid, dim3(1024), MQ_LDS_BYTES_256, stream, a);
-        return;
+// ---- the host side: launch building blocks ----
+// raise the kernel's dynamic-LDS limit (once per device), then launch. The kernel is a template argument: the limit's "done" flag is per kernel
+template <auto KERNEL> static void mmq_launch(dim3 grid, int block, size_t lds_bytes, const mmq_args & a, hipStream_t stream) {
+    MI_LDS_LIMIT_OR_DIE(lds_bytes, KERNEL);
+    hipLaunchKernelGGL(KERNEL, grid, dim3(block), lds_bytes, stream, a);
+}
+// a run-time block format as a compile-time tag: calls f(std::integral_constant<int, type>); any other type aborts with the caller's name
+template <typename F> static void mmq_dispatch_type(int type, const char * who, F && f) {
+    switch (type) {
+        case T_Q4_0:  f(std::integral_constant<int, T_Q4_0>{});  break;
+        case T_Q8_0:  f(std::integral_constant<int, T_Q8_0>{});  break;
+        case T_Q4_K:  f(std::integral_constant<int, T_Q4_K>{});  break;
+        case T_Q5_K:  f(std::integral_constant<int, T_Q5_K>{});  break;
+        case T_Q6_K:  f(std::integral_constant<int, T_Q6_K>{});  break;
+        case T_MXFP4: f(std::integral_constant<int, T_MXFP4>{}); break;
+        default: fprintf(stderr, "%s: unsupported type %d\n", who, type); abort();
     }
-    hipLaunchKernelGGL((k_mmq<T_, 256>), grid, dim3(512), MQ_LDS_BYTES_256, stream, a);
+}
+// the f32 -> bf16 (F16: f16) activation copy: rows x + i1*nb1 + i2*nb2 + i3*nb3 (n x ne2 x ne3 of them, k floats each) -> dense rows of kp(k) elements at xb
+template <bool F16> static void mmq_act_to_16(const void * x, size_t nb1, size_t nb2, size_t nb3, int64_t k, int64_t n, int64_t ne2, int64_t ne3, uint16_t * xb, hipStream_t stream) {
+    act16_args pa{};
+    pa.x = (const char *) x; pa.nb1 = nb1; pa.nb2 = nb2; pa.nb3 = nb3; pa.k = k; pa.n = n; pa.ne2 = ne2; pa.y = xb;
+    const dim3 grid((unsigned)((mmq_kp(k) + 1023)/1024), (unsigned) n, (unsigned)(ne2*ne3));
+    hipLaunchKernelGGL((k_act_to_16<F16>), grid, dim3(256), 0, stream, pa);
+}
+// the fields every launch sets: one weight tensor, one batch, no k split. Everything else is zero / NULL until the caller names it
+static mmq_args mmq_base_args(const void * W, size_t w_row_stride, size_t w_nb2, size_t w_nb3, int64_t m, int64_t k, const uint16_t * X, int64_t n,
+                              void * dst, size_t dst_nb1, size_t dst_nb2, size_t dst_nb3) {
+    mmq_args a{};
+    a.W = (const char *) W; a.w_row_stride = w_row_stride; a.w_nb2 = w_nb2; a.w_nb3 = w_nb3; a.m = (int) m; a.k = (int) k; a.X = X; a.n = (int) n;
+    a.dst = (char *) dst; a.dst_nb1 = dst_nb1; a.dst_nb2 = dst_nb2; a.dst_nb3 = dst_nb3;
+    a.ne12 = a.r2 = a.r3 = a.ksplit = 1; a.mtiles = (int)((m + MQ_BM - 1)/MQ_BM);
+    return a;
 }
 
-// (room for whole 256-token tiles + 8 rows behind the last one: k_mmq_ws copies an activation tile HBM/L2 -> LDS in 1 KiB pieces of 7 rows + one chunk; rows past n are never stored)
-static size_t mmq_x_bytes(int64_t k, int64_t n) { return ((size_t)((n + 255)/256*256 + 8)*mmq_kp(k)*2 + 255) & ~(size_t) 255; }
-size_t mul_mat_q_x_bytes(int64_t k, int64_t n) { return mmq_x_bytes(k, n); }
-size_t mul_mat_q_scratch_bytes(int64_t k, int64_t n, int64_t m) { return mmq_x_bytes(k, n) + (size_t) 4*m*n*4 + 512; }     // bf16 copy of x | up to 4 split-k planes
+// ---- the scratch of a prefill mat-mul: | bf16 copy of x | split-k planes | (kernels.h: mmq_layout) ----
+// (the copy has room for whole 256-token tiles + 8 rows behind the last one: k_mmq_ws copies an activation tile HBM/L2 -> LDS in 1 KiB pieces of 7 rows + one chunk; rows past n are never stored)
+mmq_layout mul_mat_q_layout(int64_t k, int64_t n, int64_t m, int n_planes) {
+    mmq_layout l;
+    l.x_end = ((size_t)((n + 255)/256*256 + 8)*mmq_kp(k)*2 + 255) & ~(size_t) 255;
+    l.planes_off = l.x_end;
+    l.planes_bytes = (size_t) n_planes*m*n*4;
+    l.total = l.x_end + l.planes_bytes + 512;
+    return l;
+}
+size_t mul_mat_q_x_bytes(int64_t k, int64_t n) { return mul_mat_q_layout(k, n, 0).x_end; }
+size_t mul_mat_q_scratch_bytes(int64_t k, int64_t n, int64_t m) { return mul_mat_q_layout(k, n, m).total; }     // (room for the most planes any plan asks for)
+
+// ---- the launch plan: tile size, k split and grid of one prefill launch, decided from the shape, alignment facts and switches alone ----
+// 256-token tiles of 128 weight rows: with at least this many the grid counts as filling the 256 CUs (m = 14336, n = 512: 224 workgroups do, m = 4096, n = 512: 64 do not)
+constexpr int64_t MQ_FILL_TILES = 160;
+// ok: false = this launch form does not take the shape (the caller has another way); tile: 128 | 256 tokens per workgroup; ksplit: 1 | 2 | 4 parts of k, each into
+// its own dense [n][m] f32 plane (planes_bytes in all); mtiles: tiles along the weight rows, per part; w16: the 16-wave kernel (256-token tiles only)
+struct mmq_plan { bool ok; int tile, ksplit, mtiles; dim3 grid; bool w16; size_t planes_bytes; };
+static mmq_plan mmq_plan_done(mmq_plan pl, int64_t m, int64_t n) {
+    pl.grid = dim3((unsigned)((n + pl.tile - 1)/pl.tile), (unsigned)(pl.mtiles*pl.ksplit), 1);
+    pl.planes_bytes = pl.ksplit > 1 ? (size_t) pl.ksplit*m*n*4 : 0;
+    pl.ok = true;
+    return pl;
+}
+// one weight tensor (mul_mat_q). vec_ok: rows of dst (and res) can be combined 16 bytes at a time
+static mmq_plan mmq_plan_one(int64_t m, int64_t k, int64_t n, bool vec_ok) {
+    mmq_plan pl = {};
+    pl.mtiles = (int)((m + MQ_BM - 1)/MQ_BM); pl.ksplit = 1;
+    // 256-token tiles when they still fill the chip (m = 14336, n = 512: 224 workgroups); else 128-token tiles, and a grid that would
+    // leave the chip half empty (m = 4096, n = 512: 128 tiles on 256 CUs) is split in two along k
+    const int64_t wtiles = (int64_t) pl.mtiles*((n + 255)/256);
+    // few rows (wo: m = 4096, k = 4096; ffn_down: k = 14336): 256-token tiles and k in four parts (with the 16-wave kernel this beats
+    // 128-token tiles split in two also at k = 4096: wo 49 -> 42 us)
+    static const int64_t wide4_min_k = env_int("GGML_MI355X_WIDE4_MINK", 4096);
+    const bool wide4 = n >= 256 && wtiles < MQ_FILL_TILES && wtiles*4 >= MQ_FILL_TILES && k % 1024 == 0 && k >= wide4_min_k && vec_ok;
+    const bool wide = (n >= 256 && wtiles >= MQ_FILL_TILES) || wide4;
+    pl.tile = wide ? 256 : 128;
+    const int64_t ntiles = (n + pl.tile - 1)/pl.tile;
+    if (wide4) pl.ksplit = 4;
+    else if (!wide && ntiles*pl.mtiles <= MQ_FILL_TILES && k % 512 == 0 && k >= 2048 && vec_ok) pl.ksplit = 2;
+    pl.w16 = wide && mmq_w16_on();
+    return mmq_plan_done(pl, m, n);
+}
+// 2 or 3 weight tensors, m_tot rows in `tiles` m-tiles (mul_mat_q_multi): 256-token tiles only. Not the rule above: two parts come before four, and a k that does not split
+// still goes as one launch. rope / kv_store / bias: what the caller wants to ride on the launch
+static mmq_plan mmq_plan_multi(int64_t m_tot, int tiles, int64_t k, int64_t n, bool vec_ok, bool rope, bool kv_store, bool bias) {
+    mmq_plan pl = {};
+    pl.tile = 256; pl.mtiles = tiles; pl.w16 = mmq_w16_on();
+    if (n < 256 || m_tot >= (1ll << 30)) return pl;
+    if (rope && !pl.w16) return pl;        // epilogue / combine-pass ROPE: 16-wave kernel only
+    const int64_t wt = (int64_t) tiles*((n + 255)/256);
+    if (wt >= MQ_FILL_TILES) pl.ksplit = 1;
+    else if (wt*2 >= MQ_FILL_TILES && k % 512 == 0 && k >= 2048 && vec_ok) pl.ksplit = 2;
+    else if (wt*4 >= MQ_FILL_TILES && k % 1024 == 0 && k >= 4096 && vec_ok) pl.ksplit = 4;
+    else if (wt >= 64) pl.ksplit = 1;        // k does not split (gpt-oss: 2880): still one launch of 80 tiles instead of three of 64 + 8 + 8 on 256 CUs
+    else return pl;
+    // the rotation rides on the combine pass (one sincos per pair, no lane exchange); in the mat-mul epilogue both lanes of a pair would
+    // evaluate it (measured: pp2048 -2.6 % against separate ROPE kernels), so without a k split the caller keeps its ROPE launches
+    if ((rope || kv_store) && pl.ksplit == 1) return pl;
+    if (bias && pl.ksplit != 1) return pl;          // (the bias rides on the epilogue only)
+    return mmq_plan_done(pl, m_tot, n);
+}
+// gate / up + SwiGLU (mul_mat_q_glu): taken only when the 256-token tiles fill the chip, never split
+static mmq_plan mmq_plan_glu(int64_t m, int64_t n) {
+    mmq_plan pl = {};
+    pl.tile = 256; pl.ksplit = 1; pl.mtiles = (int)((m + MQ_BM - 1)/MQ_BM);
+    pl = mmq_plan_done(pl, m, n);      // (the grid whatever ok says: mul_mat_q_glu launches what its caller asked mul_mat_q_glu_supported about)
+    pl.ok = n >= 256 && (int64_t) pl.mtiles*((n + 255)/256) >= MQ_FILL_TILES;
+    return pl;
+}
+// a launch of 256-token tiles: one weight type, or the segments' two (T2_)
+template <int T_, int T2_ = T_> static void launch_mmq_256(const mmq_plan & pl, const mmq_args & a, hipStream_t stream) {
+    if (!pl.w16) mmq_launch<k_mmq<T_, 256, false, T2_>>(pl.grid, 512, MQ_LDS_BYTES_256, a, stream);
+    else         mmq_launch<k_mmq16<T_, T2_>>(pl.grid, 1024, MQ_LDS_BYTES_256, a, stream);
+}
 
 // dst = plane 0 + plane 1 [+ plane 2 + plane 3] [+ residual], always in this order; 4 consecutive weight rows of one token per thread
 template <int NP>
@@ -1032,48 +1124,26 @@ __global__ void __launch_bounds__(256) k_combine(char * dst, size_t dst_nb1, con
 void mul_mat_q(int type_a, const void * W, size_t w_row_stride, int64_t m, int64_t k,
                const float * x, size_t x_row_stride, int64_t n, void * scratch, bool scratch_ready, float * dst, size_t dst_col_stride_bytes,
                const float * res, size_t res_row_stride, hipStream_t stream, mmq_deferred * defer) {
-    if (defer) { defer->np = 0; defer->planes = nullptr; }
+    if (defer) *defer = {};
     if (m == 0 || n == 0) return;
     uint16_t * xb = (uint16_t *) scratch;
-    if (!scratch_ready) {
-        act16_args pa = { (const char *) x, x_row_stride, 0, 0, k, n, 1, xb };
-        hipLaunchKernelGGL((k_act_to_16<false>), dim3((unsigned)((mmq_kp(k) + 1023)/1024), (unsigned) n, 1), dim3(256), 0, stream, pa);
-    }
-    mmq_args a = { (const char *) W, w_row_stride, 0, 0, (int) m, (int) k, xb, (int) n, (char *) dst, dst_col_stride_bytes, 0, 0, 1, 1, 1, 1, 0, nullptr,
-                   (const char *) res, res_row_stride, nullptr, nullptr, nullptr, 0, 0, 0 };
-    const int mtiles = (int)((m + MQ_BM - 1)/MQ_BM);
-    a.mtiles = mtiles;
-    // 256-token tiles when they still fill the chip (m = 14336, n = 512: 224 workgroups); else 128-token tiles, and a grid that would
-    // leave the chip half empty (m = 4096, n = 512: 128 tiles on 256 CUs) is split in two along k
-    const int64_t wtiles = (int64_t) mtiles*((n + 255)/256);
+    if (!scratch_ready) mmq_act_to_16<false>(x, x_row_stride, 0, 0, k, n, 1, 1, xb, stream);
     const bool vec_ok = m % 4 == 0 && dst_col_stride_bytes % 16 == 0 && ((uintptr_t) dst % 16) == 0 && (!res || (res_row_stride % 16 == 0 && ((uintptr_t) res % 16) == 0));
-    // few rows (wo: m = 4096, k = 4096; ffn_down: k = 14336): 256-token tiles and k in four parts (with the 16-wave kernel this beats
-    // 128-token tiles split in two also at k = 4096: wo 49 -> 42 us)
-    static const int64_t wide4_min_k = env_int("GGML_MI355X_WIDE4_MINK", 4096);
-    const bool wide4 = n >= 256 && wtiles < 160 && wtiles*4 >= 160 && k % 1024 == 0 && k >= wide4_min_k && vec_ok;
-    const bool wide = (n >= 256 && wtiles >= 160) || wide4;
-    const int ntiles = wide ? (int)((n + 255)/256) : (int)((n + MQ_BN - 1)/MQ_BN);
-    float * planes = (float *) ((char *) scratch + mmq_x_bytes(k, n));
-    if (wide4) a.ksplit = 4;
-    else if (!wide && (int64_t) ntiles*mtiles <= 160 && k % 512 == 0 && k >= 2048 && vec_ok) a.ksplit = 2;
-    if (a.ksplit > 1) a.dst2 = (char *) planes;
-    const dim3 grid((unsigned) ntiles, (unsigned)(mtiles*a.ksplit), 1);
-#define MI_MMQ(T_) do { if (wide) launch_mmq_wide<T_>(grid, a, stream); \
-                        else      hipLaunchKernelGGL((k_mmq<T_, 128>), grid, dim3(256), MQ_LDS_BYTES, stream, a); } while (0)
-    switch (type_a) {
-        case T_Q4_0:  MI_MMQ(T_Q4_0);  break;
-        case T_Q8_0:  MI_MMQ(T_Q8_0);  break;
-        case T_Q4_K:  MI_MMQ(T_Q4_K);  break;
-        case T_Q5_K:  MI_MMQ(T_Q5_K);  break;
-        case T_Q6_K:  MI_MMQ(T_Q6_K);  break;
-        case T_MXFP4: MI_MMQ(T_MXFP4); break;
-        default: fprintf(stderr, "mmq: unsupported type %d\n", type_a); abort();
-    }
-#undef MI_MMQ
-    if (defer && a.ksplit > 1) { defer->np = a.ksplit; defer->planes = planes; return; }
+    const mmq_plan pl = mmq_plan_one(m, k, n, vec_ok);
+    const size_t planes_off = mul_mat_q_layout(k, n, m).planes_off;
+    float * planes = (float *) ((char *) scratch + planes_off);
+    mmq_args a = mmq_base_args(W, w_row_stride, 0, 0, m, k, xb, n, dst, dst_col_stride_bytes, 0, 0);
+    a.res = (const char *) res; a.res_nb1 = res_row_stride; a.ksplit = pl.ksplit;
+    if (pl.ksplit > 1) a.dst2 = (char *) planes;
+    mmq_dispatch_type(type_a, "mmq", [&](auto t) {
+        constexpr int T_ = decltype(t)::value;
+        if (pl.tile == 256) launch_mmq_256<T_>(pl, a, stream);
+        else                hipLaunchKernelGGL((k_mmq<T_, 128>), pl.grid, dim3(256), MQ_LDS_BYTES, stream, a);
+    });
+    if (defer && pl.ksplit > 1) { defer->np = pl.ksplit; defer->planes = planes; defer->planes_off = planes_off; return; }
     const unsigned cgrid = (unsigned)((m/4*n + 255)/256);
-    if (a.ksplit == 4)      hipLaunchKernelGGL(k_combine<4>, dim3(cgrid), dim3(256), 0, stream, (char *) dst, dst_col_stride_bytes, planes, (const char *) res, res_row_stride, m/4, n);
-    else if (a.ksplit == 2) hipLaunchKernelGGL(k_combine<2>, dim3(cgrid), dim3(256), 0, stream, (char *) dst, dst_col_stride_bytes, planes, (const char *) res, res_row_stride, m/4, n);
+    if (pl.ksplit == 4)      hipLaunchKernelGGL(k_combine<4>, dim3(cgrid), dim3(256), 0, stream, (char *) dst, dst_col_stride_bytes, planes, (const char *) res, res_row_stride, m/4, n);
+    else if (pl.ksplit == 2) hipLaunchKernelGGL(k_combine<2>, dim3(cgrid), dim3(256), 0, stream, (char *) dst, dst_col_stride_bytes, planes, (const char *) res, res_row_stride, m/4, n);
 }
 
 // ---- several mat-muls on the same activations as one launch (wq / wk / wv of build_attn, src/llama-model.cpp:6017-6040) ----
@@ -1107,26 +1177,13 @@ __global__ void __launch_bounds__(256) k_combine_seg(const combine_seg_args p) {
     }
 }
 
-template <int T_, int T2_>
-static void launch_mmq_multi(dim3 grid, const mmq_args & a, hipStream_t stream) {
-    MI_LDS_LIMIT_OR_DIE(MQ_LDS_BYTES_256, k_mmq<T_, 256, false, T2_>);
-    const bool w16 = mmq_w16_on();
-    if (w16) {
-        MI_LDS_LIMIT_OR_DIE(MQ_LDS_BYTES_256, k_mmq16<T_, T2_>);
-        hipLaunchKernelGGL((k_mmq16<T_, T2_>), grid, dim3(1024), MQ_LDS_BYTES_256, stream, a);
-        return;
-    }
-    hipLaunchKernelGGL((k_mmq<T_, 256, false, T2_>), grid, dim3(512), MQ_LDS_BYTES_256, stream, a);
-}
-
 // false: not done (too few tiles for 256-token tiles, an unsupported mix of types, scratch too small) — the caller runs them one by one
 bool mul_mat_q_multi(int nseg, const int * types, const void * const * W, const size_t * w_row_stride, const int64_t * m, float * const * dst, const size_t * dst_stride,
                      int64_t k, const float * x, size_t x_row_stride, int64_t n, void * scratch, size_t scratch_size, bool scratch_ready,
                      const mmvq_rope * rope, const int * seg_rope, const mmq_kv_store * kvs, hipStream_t stream, const float * const * seg_bias) {
-    if (nseg < 2 || nseg > 3 || n < 256) return false;
-    const bool w16 = mmq_w16_on();
-    if (rope) {        // epilogue / combine-pass ROPE: 16-wave kernel only, heads of an even size that start at column multiples of 4
-        if (!w16 || rope->head_dim % 4 != 0 || rope->p.n_dims % 2 != 0) return false;
+    if (nseg < 2 || nseg > 3) return false;
+    if (rope) {        // heads of an even size that start at column multiples of 4
+        if (rope->head_dim % 4 != 0 || rope->p.n_dims % 2 != 0) return false;
         for (int s = 0; s < nseg; s++) if (seg_rope[s] && m[s] % rope->head_dim != 0) return false;
     }
     int t1 = types[0], t2 = types[0];
@@ -1135,96 +1192,59 @@ bool mul_mat_q_multi(int nseg, const int * types, const void * const * W, const 
         if (t1 == T_Q6_K) { const int t = t1; t1 = t2; t2 = t; }
         if (!(t2 == T_Q6_K && (t1 == T_Q4_K || t1 == T_Q5_K))) return false;       // the mixed pairs of the K-quant mixes (attn_v one step up)
     }
-    mmq_args a = { nullptr, 0, 0, 0, 0, (int) k, (const uint16_t *) scratch, (int) n, nullptr, 0, 0, 0, 1, 1, 1, 1, 0, nullptr, nullptr, 0, nullptr, nullptr, nullptr, 0, 0, 0 };
+    mmq_args a = mmq_base_args(nullptr, 0, 0, 0, 0, k, (const uint16_t *) scratch, n, nullptr, 0, 0, 0);
     a.nseg = nseg;
     int64_t m_tot = 0; int tiles = 0; bool vec_ok = true;
     for (int s = 0; s < nseg; s++) {
-        a.seg[s] = { (const char *) W[s], (char *) dst[s], w_row_stride[s], dst_stride[s], (int) m[s], tiles, (int) m_tot, types[s] != t1 ? 1 : 0, rope && seg_rope[s] ? 1 : 0,
-                     seg_bias ? seg_bias[s] : nullptr };
+        mmq_seg & g = a.seg[s];
+        g.W = (const char *) W[s]; g.dst = (char *) dst[s]; g.w_row_stride = w_row_stride[s]; g.dst_nb1 = dst_stride[s]; g.m = (int) m[s]; g.tile0 = tiles; g.col0 = (int) m_tot;
+        g.type2 = types[s] != t1 ? 1 : 0; g.rope = rope && seg_rope[s] ? 1 : 0; g.bias = seg_bias ? seg_bias[s] : nullptr;
         vec_ok = vec_ok && m[s] % 4 == 0 && dst_stride[s] % 16 == 0 && ((uintptr_t) dst[s] % 16) == 0;
         m_tot += m[s]; tiles += (int)((m[s] + MQ_BM - 1)/MQ_BM);
     }
     if (nseg < 3) a.seg[2] = a.seg[1];
     if (rope) a.rope = make_fused_rope(*rope);
-    if (m_tot >= (1ll << 30)) return false;
-    a.m = (int) m_tot; a.mtiles = tiles;
-    const int ntiles = (int)((n + 255)/256);
-    const int64_t wt = (int64_t) tiles*ntiles;
-    if (wt >= 160) a.ksplit = 1;
-    else if (wt*2 >= 160 && k % 512 == 0 && k >= 2048 && vec_ok) a.ksplit = 2;
-    else if (wt*4 >= 160 && k % 1024 == 0 && k >= 4096 && vec_ok) a.ksplit = 4;
-    else if (wt >= 64) a.ksplit = 1;        // k does not split (gpt-oss: 2880): still one launch of 80 tiles instead of three of 64 + 8 + 8 on 256 CUs
-    else return false;
-    // the rotation rides on the combine pass (one sincos per pair, no lane exchange); in the mat-mul epilogue both lanes of a pair would
-    // evaluate it (measured: pp2048 -2.6 % against separate ROPE kernels), so without a k split the caller keeps its ROPE launches
-    if ((rope || kvs) && a.ksplit == 1) return false;
-    if (seg_bias && a.ksplit != 1) return false;          // (the bias rides on the epilogue only)
-    if (mmq_x_bytes(k, n) + (a.ksplit > 1 ? (size_t) a.ksplit*m_tot*n*4 : 0) + 512 > scratch_size) return false;
-    if (!scratch_ready) {
-        act16_args pa = { (const char *) x, x_row_stride, 0, 0, k, n, 1, (uint16_t *) scratch };
-        hipLaunchKernelGGL((k_act_to_16<false>), dim3((unsigned)((mmq_kp(k) + 1023)/1024), (unsigned) n, 1), dim3(256), 0, stream, pa);
-    }
-    float * planes = (float *) ((char *) scratch + mmq_x_bytes(k, n));
-    if (a.ksplit > 1) a.dst2 = (char *) planes;
-    const dim3 grid((unsigned) ntiles, (unsigned)(tiles*a.ksplit), 1);
+    const mmq_plan pl = mmq_plan_multi(m_tot, tiles, k, n, vec_ok, rope != nullptr, kvs != nullptr, seg_bias != nullptr);
+    if (!pl.ok) return false;
+    const mmq_layout lay = mul_mat_q_layout(k, n, m_tot, pl.ksplit > 1 ? pl.ksplit : 0);
+    if (lay.total > scratch_size) return false;
+    a.m = (int) m_tot; a.mtiles = tiles; a.ksplit = pl.ksplit;
+    if (!scratch_ready) mmq_act_to_16<false>(x, x_row_stride, 0, 0, k, n, 1, 1, (uint16_t *) scratch, stream);
+    float * planes = (float *) ((char *) scratch + lay.planes_off);
+    if (pl.ksplit > 1) a.dst2 = (char *) planes;
     if (t1 != t2) {
-        if (t1 == T_Q4_K) launch_mmq_multi<T_Q4_K, T_Q6_K>(grid, a, stream); else launch_mmq_multi<T_Q5_K, T_Q6_K>(grid, a, stream);
-    } else switch (t1) {
-        case T_Q4_0:  launch_mmq_wide<T_Q4_0>(grid, a, stream);  break;
-        case T_Q8_0:  launch_mmq_wide<T_Q8_0>(grid, a, stream);  break;
-        case T_Q4_K:  launch_mmq_wide<T_Q4_K>(grid, a, stream);  break;
-        case T_Q5_K:  launch_mmq_wide<T_Q5_K>(grid, a, stream);  break;
-        case T_Q6_K:  launch_mmq_wide<T_Q6_K>(grid, a, stream);  break;
-        case T_MXFP4: launch_mmq_wide<T_MXFP4>(grid, a, stream); break;
-        default: fprintf(stderr, "mmq_multi: unsupported type %d\n", t1); abort();
-    }
-    if (a.ksplit > 1) {
-        combine_seg_args ca = { planes, m_tot/4, n, nseg, { nullptr, nullptr, nullptr }, { 0, 0, 0 }, { 0, 0, 0 }, { 0, 0, 0 }, a.rope,
-                                { nullptr, nullptr, nullptr }, { nullptr, nullptr, nullptr }, { 0, 0, 0 }, { 0, 0, 0 }, { 0, 0, 0 } };
+        if (t1 == T_Q4_K) launch_mmq_256<T_Q4_K, T_Q6_K>(pl, a, stream); else launch_mmq_256<T_Q5_K, T_Q6_K>(pl, a, stream);
+    } else mmq_dispatch_type(t1, "mmq_multi", [&](auto t) { launch_mmq_256<decltype(t)::value>(pl, a, stream); });
+    if (pl.ksplit > 1) {
+        combine_seg_args ca{};
+        ca.planes = planes; ca.m4_tot = m_tot/4; ca.n = n; ca.nseg = nseg; ca.rope = a.rope;
         if (kvs) for (int s = 0; s < nseg; s++) { ca.st16[s] = kvs->st16[s]; ca.st_idx[s] = kvs->st_idx[s]; ca.st_row_elems[s] = kvs->st_row_elems[s]; ca.st_mode[s] = kvs->st_mode[s]; ca.m_seg[s] = (int) m[s]; }
         for (int s = 0; s < 3; s++) { const int q = s < nseg ? s : nseg - 1; ca.dst[s] = a.seg[q].dst; ca.dst_nb1[s] = a.seg[q].dst_nb1; ca.col4[s] = a.seg[q].col0/4; ca.rope_seg[s] = a.seg[q].rope; }
         const unsigned cgrid = (unsigned)((m_tot/4*n + 255)/256);
-        if (a.ksplit == 4) hipLaunchKernelGGL(k_combine_seg<4>, dim3(cgrid), dim3(256), 0, stream, ca);
-        else               hipLaunchKernelGGL(k_combine_seg<2>, dim3(cgrid), dim3(256), 0, stream, ca);
+        if (pl.ksplit == 4) hipLaunchKernelGGL(k_combine_seg<4>, dim3(cgrid), dim3(256), 0, stream, ca);
+        else                hipLaunchKernelGGL(k_combine_seg<2>, dim3(cgrid), dim3(256), 0, stream, ca);
     }
     return true;
 }
 
 // gate / up + SwiGLU of build_ffn (src/llama-graph.cpp:632-774) for many tokens: dst[n][m] = silu(Wg.x) * (Wu.x)
-template <int T_>
-static void launch_mmq_dual(dim3 grid, const mmq_args & a, hipStream_t stream) {
-    // the wave-specialized kernel where its producers' four register stages fit (Q4_K, MXFP4: 168 registers, no scratch; the other formats' raw blocks are larger and spill)
-    if constexpr (T_ == T_Q4_K || T_ == T_MXFP4) if (mmq_ws_on()) {
-        MI_LDS_LIMIT_OR_DIE(MQ_LDS_BYTES_WS256, k_mmq_ws<T_, 256, true>);
-        hipLaunchKernelGGL((k_mmq_ws<T_, 256, true>), grid, dim3(768), MQ_LDS_BYTES_WS256, stream, a);
-        return;
-    }
-    MI_LDS_LIMIT_OR_DIE(MQ_LDS_BYTES_DUAL, k_mmq<T_, 256, true>);
-    hipLaunchKernelGGL((k_mmq<T_, 256, true>), grid, dim3(512), MQ_LDS_BYTES_DUAL, stream, a);
-}
-bool mul_mat_q_glu_supported(int64_t m, int64_t n) { return n >= 256 && ((m + MQ_BM - 1)/MQ_BM)*((n + 255)/256) >= 160; }
+bool mul_mat_q_glu_supported(int64_t m, int64_t n) { return mmq_plan_glu(m, n).ok; }
 void mul_mat_q_glu(int type_a, const void * Wg, const void * Wu, size_t w_row_stride, int64_t m, int64_t k,
                    const float * x, size_t x_row_stride, int64_t n, void * scratch, bool scratch_ready, float * dst, size_t dst_col_stride_bytes, hipStream_t stream,
                    uint16_t * y16) {
     if (m == 0 || n == 0) return;
     uint16_t * xb = (uint16_t *) scratch;
-    if (!scratch_ready) {
-        act16_args pa = { (const char *) x, x_row_stride, 0, 0, k, n, 1, xb };
-        hipLaunchKernelGGL((k_act_to_16<false>), dim3((unsigned)((mmq_kp(k) + 1023)/1024), (unsigned) n, 1), dim3(256), 0, stream, pa);
-    }
-    mmq_args a = { (const char *) Wg, w_row_stride, 0, 0, (int) m, (int) k, xb, (int) n, (char *) dst, dst_col_stride_bytes, 0, 0, 1, 1, 1, 1, 0, nullptr, nullptr, 0, y16, (const char *) Wu, nullptr, 0, 0, 0 };
-    a.mtiles = (int)((m + MQ_BM - 1)/MQ_BM);
+    if (!scratch_ready) mmq_act_to_16<false>(x, x_row_stride, 0, 0, k, n, 1, 1, xb, stream);
+    const mmq_plan pl = mmq_plan_glu(m, n);
+    mmq_args a = mmq_base_args(Wg, w_row_stride, 0, 0, m, k, xb, n, dst, dst_col_stride_bytes, 0, 0);
+    a.W2 = (const char *) Wu; a.y16 = y16;
     { static const int dbg = (int) env_int("GGML_MI355X_MMQ_DBG", 0); a.dbg = dbg; }
-    const dim3 grid((unsigned)((n + 255)/256), (unsigned) a.mtiles, 1);
-    switch (type_a) {
-        case T_Q4_0:  launch_mmq_dual<T_Q4_0>(grid, a, stream);  break;
-        case T_Q8_0:  launch_mmq_dual<T_Q8_0>(grid, a, stream);  break;
-        case T_Q4_K:  launch_mmq_dual<T_Q4_K>(grid, a, stream);  break;
-        case T_Q5_K:  launch_mmq_dual<T_Q5_K>(grid, a, stream);  break;
-        case T_Q6_K:  launch_mmq_dual<T_Q6_K>(grid, a, stream);  break;
-        case T_MXFP4: launch_mmq_dual<T_MXFP4>(grid, a, stream); break;
-        default: fprintf(stderr, "mmq_glu: unsupported type %d\n", type_a); abort();
-    }
+    mmq_dispatch_type(type_a, "mmq_glu", [&](auto t) {
+        constexpr int T_ = decltype(t)::value;
+        // the wave-specialized kernel where its producers' four register stages fit (Q4_K, MXFP4: 168 registers, no scratch; the other formats' raw blocks are larger and spill)
+        if constexpr (T_ == T_Q4_K || T_ == T_MXFP4) if (mmq_ws_on()) { mmq_launch<k_mmq_ws<T_, 256, true>>(pl.grid, 768, MQ_LDS_BYTES_WS256, a, stream); return; }
+        mmq_launch<k_mmq<T_, 256, true>>(pl.grid, 512, MQ_LDS_BYTES_DUAL, a, stream);
+    });
 }
 
 // ---- MUL_MAT_ID for many tokens: pairs (token, slot) sorted by expert, then the tiled kernel above per (expert, 128 pairs) ----
@@ -1263,16 +1283,17 @@ static int moe_max_tiles(int64_t n_pairs, int64_t n_expert) { return (int)(n_pai
 static size_t moe_table_bytes(int64_t n_pairs, int64_t n_expert) { return ((size_t)(1 + 3*moe_max_tiles(n_pairs, n_expert) + n_pairs)*4 + 255) & ~(size_t) 255; }
 bool mul_mat_q_id_supported(int64_t n_expert, int64_t n_used, int64_t n_tokens) { return n_expert <= 256 && n_used*n_tokens < (1 << 24); }
 size_t mul_mat_q_id_scratch_bytes(int64_t k, int64_t n_b, int64_t n_tokens, int64_t n_used, int64_t n_expert) {
-    return mmq_x_bytes(k, n_b*n_tokens) + moe_table_bytes(n_used*n_tokens, n_expert) + 256;
+    return mul_mat_q_layout(k, n_b*n_tokens, 0).x_end + moe_table_bytes(n_used*n_tokens, n_expert) + 256;
 }
-// the fused expert chain (gate / up / GLU -> down): bf16 copy of the layer input | tile table | bf16 GLU result, one row per (token, slot) pair
+// the fused expert chain (gate / up / GLU -> down): bf16 copy of the layer input | tile table | tile table 2 | bf16 GLU result, one row per (token, slot) pair
 mmq_moe_plan mul_mat_q_id_plan(void * scratch, int64_t k, int64_t n_tokens, int64_t n_used, int64_t n_expert, int64_t m_glu) {
+    const size_t x_end = mul_mat_q_layout(k, n_tokens, 0).x_end, table_bytes = moe_table_bytes(n_used*n_tokens, n_expert);
     mmq_moe_plan pl;
     pl.xb = (uint16_t *) scratch;
-    pl.table = (int *) ((char *) scratch + mmq_x_bytes(k, n_tokens));
-    pl.table2 = (int *) ((char *) pl.table + moe_table_bytes(n_used*n_tokens, n_expert));
-    pl.y16 = (uint16_t *) ((char *) pl.table2 + moe_table_bytes(n_used*n_tokens, n_expert));
-    pl.bytes = mmq_x_bytes(k, n_tokens) + 2*moe_table_bytes(n_used*n_tokens, n_expert) + (((size_t) n_used*n_tokens*mmq_kp(m_glu)*2 + 255) & ~(size_t) 255) + 256;
+    pl.table = (int *) ((char *) scratch + x_end);
+    pl.table2 = (int *) ((char *) pl.table + table_bytes);
+    pl.y16 = (uint16_t *) ((char *) pl.table2 + table_bytes);
+    pl.bytes = x_end + 2*table_bytes + (((size_t) n_used*n_tokens*mmq_kp(m_glu)*2 + 255) & ~(size_t) 255) + 256;
     return pl;
 }
 int mul_mat_q_id_tile(int64_t n_used, int64_t n_tokens, int64_t n_expert) {
@@ -1287,22 +1308,7 @@ void mul_mat_q_id_sort(const int32_t * ids, size_t ids_nb0, size_t ids_nb1, int6
     hipLaunchKernelGGL(k_moe_sort, dim3(1), dim3(256), 0, stream, ps);
 }
 void mul_mat_q_id_act16(const float * b, size_t b_nb1, size_t b_nb2, int64_t k, int64_t n_b, int64_t n_tokens, uint16_t * xb, hipStream_t stream) {
-    act16_args pa = { (const char *) b, b_nb1, b_nb2, 0, k, n_b, n_tokens, xb };     // dense [token][n_b][k] bf16
-    hipLaunchKernelGGL((k_act_to_16<false>), dim3((unsigned)((mmq_kp(k) + 1023)/1024), (unsigned) n_b, (unsigned) n_tokens), dim3(256), 0, stream, pa);
-}
-
-template <int T_>
-static void launch_mmq_moe(dim3 grid, const mmq_args & a, int tile, bool dual, hipStream_t stream) {
-    if (dual) {
-        MI_LDS_LIMIT_OR_DIE(MQ_LDS_BYTES_DUAL, k_mmq<T_, 256, true, T_, true>);
-        hipLaunchKernelGGL((k_mmq<T_, 256, true, T_, true>), grid, dim3(512), MQ_LDS_BYTES_DUAL, stream, a);
-    } else if (tile == 256) {
-        MI_LDS_LIMIT_OR_DIE(MQ_LDS_BYTES_256, k_mmq16<T_, T_, true>);
-        hipLaunchKernelGGL((k_mmq16<T_, T_, true>), grid, dim3(1024), MQ_LDS_BYTES_256, stream, a);
-    } else {
-        MI_LDS_LIMIT_OR_DIE(MQ_LDS_BYTES, k_mmq<T_, 128, false, T_, true>);
-        hipLaunchKernelGGL((k_mmq<T_, 128, false, T_, true>), grid, dim3(256), MQ_LDS_BYTES, stream, a);
-    }
+    mmq_act_to_16<false>(b, b_nb1, b_nb2, 0, k, n_b, n_tokens, 1, xb, stream);     // dense [token][n_b][k] bf16
 }
 
 // the tiled kernel over a sorted pair table. xb: bf16 rows [token][n_b][kp(k)] (n_b == 1: every slot of a token reads the token's row; n_b == n_used: a row per pair);
@@ -1312,25 +1318,19 @@ void mul_mat_q_id_tiles(int type_a, const void * W, const void * W2, size_t w_ro
                         const mmq_moe_epi & epi, float * dst, size_t dst_nb1, size_t dst_nb2, uint16_t * y16, hipStream_t stream) {
     if (m == 0 || n_used*n_tokens == 0) return;
     if (W2 && tile != 256) { fprintf(stderr, "mmq_id: the dual kernel runs 256-pair tiles\n"); abort(); }
-    const int max_tiles = moe_max_tiles(n_used*n_tokens, n_expert);
-    mmq_args a = { (const char *) W, w_row_stride, w_expert_stride, 0, (int) m, (int) k, xb, (int)(n_used*n_tokens), (char *) dst, dst_nb1, dst_nb2, 0, 1, 1, 1, 1, 0, nullptr, nullptr, 0, y16, (const char *) W2,
-                   table, max_tiles, (int) n_used, (int) n_b };
-    a.mtiles = (int)((m + MQ_BM - 1)/MQ_BM);
+    mmq_args a = mmq_base_args(W, w_row_stride, w_expert_stride, 0, m, k, xb, n_used*n_tokens, dst, dst_nb1, dst_nb2, 0);
+    a.y16 = y16; a.W2 = (const char *) W2;
+    a.moe = table; a.moe_max_tiles = moe_max_tiles(n_used*n_tokens, n_expert); a.n_used = (int) n_used; a.n_b = (int) n_b;
     a.bias = epi.bias; a.bias2 = epi.bias2; a.bias_stride = epi.bias_stride; a.scale = epi.scale; a.scale_nb0 = epi.scale_nb0; a.scale_nb1 = epi.scale_nb1;
     a.glu_oai = epi.oai; a.glu_alpha = epi.alpha; a.glu_limit = epi.limit;
     a.glu_up = (const char *) epi.glu_up; a.glu_up_nb1 = epi.glu_up_nb1; a.glu_up_nb2 = epi.glu_up_nb2;
-    const dim3 grid((unsigned) max_tiles, (unsigned) a.mtiles, 1);
-#define MI_MMQ(T_) launch_mmq_moe<T_>(grid, a, tile, W2 != nullptr, stream)
-    switch (type_a) {
-        case T_Q4_0:  MI_MMQ(T_Q4_0);  break;
-        case T_Q8_0:  MI_MMQ(T_Q8_0);  break;
-        case T_Q4_K:  MI_MMQ(T_Q4_K);  break;
-        case T_Q5_K:  MI_MMQ(T_Q5_K);  break;
-        case T_Q6_K:  MI_MMQ(T_Q6_K);  break;
-        case T_MXFP4: MI_MMQ(T_MXFP4); break;
-        default: fprintf(stderr, "mmq_id: unsupported type %d\n", type_a); abort();
-    }
-#undef MI_MMQ
+    const dim3 grid((unsigned) a.moe_max_tiles, (unsigned) a.mtiles, 1);
+    mmq_dispatch_type(type_a, "mmq_id", [&](auto t) {
+        constexpr int T_ = decltype(t)::value;
+        if (W2)               mmq_launch<k_mmq<T_, 256, true, T_, true>>(grid, 512, MQ_LDS_BYTES_DUAL, a, stream);
+        else if (tile == 256) mmq_launch<k_mmq16<T_, T_, true>>(grid, 1024, MQ_LDS_BYTES_256, a, stream);
+        else                  mmq_launch<k_mmq<T_, 128, false, T_, true>>(grid, 256, MQ_LDS_BYTES, a, stream);
+    });
 }
 
 void mul_mat_q_id(int type_a, const void * W, size_t w_row_stride, size_t w_expert_stride, int64_t m, int64_t k,
@@ -1338,8 +1338,8 @@ void mul_mat_q_id(int type_a, const void * W, size_t w_row_stride, size_t w_expe
                   const int32_t * ids, size_t ids_nb0, size_t ids_nb1, int64_t n_used, int64_t n_tokens, int64_t n_expert,
                   void * scratch, float * dst, size_t dst_nb1, size_t dst_nb2, hipStream_t stream) {
     if (m == 0 || n_used*n_tokens == 0) return;
-    uint16_t * xb = (uint16_t *) scratch;
-    int * table = (int *) ((char *) scratch + mmq_x_bytes(k, n_b*n_tokens));
+    uint16_t * xb = (uint16_t *) scratch;      // bf16 copy of the input | tile table, as mul_mat_q_id_scratch_bytes sizes them
+    int * table = (int *) ((char *) scratch + mul_mat_q_layout(k, n_b*n_tokens, 0).x_end);
     const int tile = mul_mat_q_id_tile(n_used, n_tokens, n_expert);
     mul_mat_q_id_act16(b, b_nb1, b_nb2, k, n_b, n_tokens, xb, stream);
     mul_mat_q_id_sort(ids, ids_nb0, ids_nb1, n_used, n_tokens, n_expert, tile, table, stream);
@@ -1351,17 +1351,15 @@ bool mul_mat_dense_mfma_supported(const mm_dense_args & p) {
     return p.type_a == T_F16 && p.type_b == T_F32 && p.nb00 == 2 && p.nb10 == 4 && p.ne11 > MMVQ_MAX_N && p.ne00 % 32 == 0 &&
            p.ne12*p.ne13 <= 65535 && p.ne01 < (1ll << 30) && p.ne11 < (1ll << 30);
 }
-size_t mul_mat_dense_mfma_scratch_bytes(const mm_dense_args & p) { return mmq_x_bytes(p.ne10, p.ne11*p.ne12*p.ne13) + 256; }
+size_t mul_mat_dense_mfma_scratch_bytes(const mm_dense_args & p) { return mul_mat_q_layout(p.ne10, p.ne11*p.ne12*p.ne13, 0).x_end + 256; }     // the f16 copy of b only
 
 void mul_mat_dense_mfma(const mm_dense_args & p, void * scratch, hipStream_t stream) {
     if (p.ne01 == 0 || p.ne11 == 0 || p.ne12*p.ne13 == 0) return;
     uint16_t * xb = (uint16_t *) scratch;
-    const int64_t nbatch = p.ne12*p.ne13;
-    act16_args pa = { (const char *) p.b, p.nb11, p.nb12, p.nb13, p.ne10, p.ne11, p.ne12, xb };
-    hipLaunchKernelGGL((k_act_to_16<true>), dim3((unsigned)((mmq_kp(p.ne10) + 1023)/1024), (unsigned) p.ne11, (unsigned) nbatch), dim3(256), 0, stream, pa);
-    mmq_args a = { (const char *) p.a, p.nb01, p.nb02, p.nb03, (int) p.ne01, (int) p.ne00, xb, (int) p.ne11, (char *) p.dst, p.nb1, p.nb2, p.nb3,
-                   (int) p.ne12, (int)(p.ne12/p.ne02), (int)(p.ne13/p.ne03), 1, 0, nullptr, nullptr, 0, nullptr, nullptr, nullptr, 0, 0, 0 };
-    const dim3 grid((unsigned)((p.ne11 + MQ_BN - 1)/MQ_BN), (unsigned)((p.ne01 + MQ_BM - 1)/MQ_BM), (unsigned) nbatch);
+    mmq_act_to_16<true>(p.b, p.nb11, p.nb12, p.nb13, p.ne10, p.ne11, p.ne12, p.ne13, xb, stream);
+    mmq_args a = mmq_base_args(p.a, p.nb01, p.nb02, p.nb03, p.ne01, p.ne00, xb, p.ne11, p.dst, p.nb1, p.nb2, p.nb3);
+    a.ne12 = (int) p.ne12; a.r2 = (int)(p.ne12/p.ne02); a.r3 = (int)(p.ne13/p.ne03);
+    const dim3 grid((unsigned)((p.ne11 + MQ_BN - 1)/MQ_BN), (unsigned) a.mtiles, (unsigned)(p.ne12*p.ne13));
     hipLaunchKernelGGL((k_mmq<T_F16>), grid, dim3(256), MQ_LDS_BYTES, stream, a);
 }
 
