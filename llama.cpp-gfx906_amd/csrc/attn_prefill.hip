@@ -54,16 +54,24 @@ constexpr int APF_KLD = 16;     // LDS row padding (bytes): K rows HD*2 + 16 (ds
 // whose mask is -inf for all its 32 x 32 pairs (the causal future); staging and barriers go on.
 // KS = 2 (few workgroups, i.e. short prompts: the cell loop is the critical path): an iteration stages TWO cell blocks, the waves of a
 // (head, query tile) come in pairs — one per block — and the pair's states are merged through LDS at the end: half the iterations.
-template <int HD, bool VT, int MASK, int KS>
-__global__ void __launch_bounds__(64*APF_NW) k_attn_prefill(const attn_pf_args p, int hpw) {
-    constexpr int NC = HD/16, NDT = HD/32, CPR = HD/8;                 // CPR: 16-byte chunks per K row
-    constexpr int KROW = HD*2 + APF_KLD, VROW = 64 + 8, KBLK = 32*KROW, VBLK = HD*VROW;
+// HD / HDV: the sizes of a K and a V row (flash attention: every pair of attn_fa_head_sizes, with the transposed V copy). NC comes from HD, the NDT output
+// tiles of 32 dims from HDV: 80 is computed as 96, rows 80..95 of V^T zero in LDS and never stored. Staging takes KTR / VTR trips of the workgroup per block.
+// NW: waves per workgroup. 192 and 256 run with 4: their accumulators (NDT x 16) and Q (NC x 4 registers) need more than the 256 registers a lane has
+// when two waves share a SIMD.
+template <int HD, bool VT, int MASK, int KS, int HDV = HD, int NW = APF_NW>
+__global__ void __launch_bounds__(64*NW) k_attn_prefill(const attn_pf_args p, int hpw) {
+    constexpr int NC = HD/16, NDT = (HDV + 31)/32, CPR = HD/8, NT = 64*NW;      // CPR: 16-byte chunks per K row
+    constexpr int HDVP = 32*NDT;                                        // V^T rows in LDS
+    constexpr int KROW = HD*2 + APF_KLD, VROW = 64 + 8, KBLK = 32*KROW, VBLK = HDVP*VROW;
+    constexpr int KTR = (32*CPR + NT - 1)/NT, VTR = VT ? (HDV*4 + NT - 1)/NT : KTR;
+    static_assert(HD % 16 == 0 && HDV % 8 == 0, "S-product chunks of 16 dims; stores of 4 dims");
+    static_assert(VT || (HDV == HD && KTR == 1 && NW == APF_NW), "row-major V: head size 64 / 128");
     extern __shared__ __attribute__((aligned(16))) char lds_all[];     // K: [2][KS][KBLK] | V^T: [2][KS][VBLK]
     char * const ldsk_base = lds_all, * const ldsv_base = lds_all + 2*KS*KBLK;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, ql = lane & 31, hf = lane >> 5;
     const int h = blockIdx.y*hpw + wave % hpw, hk = h/(p.n_head/p.n_head_kv);
     const int ks = KS > 1 ? (wave/hpw) & (KS - 1) : 0;                  // which of the iteration's blocks this wave multiplies
-    const int q0 = (blockIdx.x*(APF_NW/(hpw*KS)) + wave/(hpw*KS))*32;
+    const int q0 = (blockIdx.x*(NW/(hpw*KS)) + wave/(hpw*KS))*32;
     const bool active = q0 < p.T;                        // wave-uniform; an idle wave still stages and meets the barriers
     const int t = min(q0 + ql, p.T - 1);
 
@@ -87,22 +95,35 @@ __global__ void __launch_bounds__(64*APF_NW) k_attn_prefill(const attn_pf_args p
     const float scale2 = p.scale*LOG2E;
     const float slope = p.max_bias > 0.0f ? (h < p.n_head_log2 ? powf(p.m0, (float)(h + 1)) : powf(p.m1, (float)(2*(h - p.n_head_log2) + 1))) : 1.0f;
 
-    // staging roles. K (and a row-major V): thread -> (cell = tid / CPR, 16-byte chunk); transposed V: thread -> (dim row = tid / 4, 8 cells)
-    const bool k_role = tid < 32*CPR, v_role = VT ? tid < HD*4 : k_role;
-    const int kcell = tid / CPR, kch = tid % CPR, vrow = tid >> 2, vch = tid & 3;
-    const char * kg = p.k + (size_t) hk*p.k_nb2 + (size_t) kch*16;
-    const char * vg = VT ? p.v + (size_t) hk*p.v_nb2 + (size_t) min(vrow, HD - 1)*p.v_nb1 + (size_t) vch*16
-                         : p.v + (size_t) hk*p.v_nb2 + (size_t) kch*16;
+    // staging roles, piece e = tid + trip*NT. K (and a row-major V): e -> (cell = e / CPR, 16-byte chunk); transposed V: e -> (dim row = e / 4, 8 cells)
+    const char * kg[KTR]; const char * vg[VTR];
+#pragma unroll
+    for (int r = 0; r < KTR; r++) kg[r] = p.k + (size_t) hk*p.k_nb2 + (size_t)((tid + r*NT) % CPR)*16;
+#pragma unroll
+    for (int r = 0; r < VTR; r++) vg[r] = VT ? p.v + (size_t) hk*p.v_nb2 + (size_t) min((tid + r*NT) >> 2, HDV - 1)*p.v_nb1 + (size_t)(tid & 3)*16
+                                             : p.v + (size_t) hk*p.v_nb2 + (size_t)(tid % CPR)*16;
     const char * mrow = MASK ? p.mask + (size_t) t*p.m_nb1 : nullptr;
+    if constexpr (HDVP != HDV) {       // the output tiles' rows past V's size: zero, in every staging buffer, once
+        constexpr int NZ = (HDVP - HDV)*VROW/8;
+        for (int i = tid; i < 2*KS*NZ; i += NT) *(int2v *) (ldsv_base + (i / NZ)*VBLK + HDV*VROW + (i % NZ)*8) = int2v{ 0, 0 };
+    }
 
-    int4v kst[KS], vst[KS];            // the next iteration's K / V pieces
+    int4v kst[KS][KTR], vst[KS][VTR];  // the next iteration's K / V pieces
     int4v mst[4];                      // the next block's mask values of this lane (f16: .xy used)
     auto fetch = [&](int kv0) {        // kv0 = first cell of the iteration (KS blocks)
 #pragma unroll
         for (int b = 0; b < KS; b++) {
             const int kvb = min(kv0 + 32*b, p.n_kv - 32);
-            if (k_role) kst[b] = *(const int4v *) (kg + (size_t)(kvb + min(kcell, 31))*p.k_nb1);
-            if (v_role) vst[b] = VT ? *(const int4v *) (vg + (size_t) kvb*2) : *(const int4v *) (vg + (size_t)(kvb + min(kcell, 31))*p.v_nb1);
+#pragma unroll
+            for (int r = 0; r < KTR; r++) {
+                const int e = tid + r*NT, kcell = e / CPR;
+                if (e < 32*CPR) kst[b][r] = *(const int4v *) (kg[r] + (size_t)(kvb + min(kcell, 31))*p.k_nb1);
+            }
+#pragma unroll
+            for (int r = 0; r < VTR; r++) {
+                const int e = tid + r*NT;
+                if (VT ? e < HDV*4 : e < 32*CPR) vst[b][r] = VT ? *(const int4v *) (vg[r] + (size_t) kvb*2) : *(const int4v *) (vg[r] + (size_t)(kvb + min(e / CPR, 31))*p.v_nb1);
+            }
         }
         const int kvc = min(kv0 + 32*ks, p.n_kv - 32);
         if (MASK == 2) {
@@ -117,15 +138,25 @@ __global__ void __launch_bounds__(64*APF_NW) k_attn_prefill(const attn_pf_args p
 #pragma unroll
         for (int b = 0; b < KS; b++) {
             char * lk = ldsk_base + (buf*KS + b)*KBLK, * lv = ldsv_base + (buf*KS + b)*VBLK;
-            if (k_role) *(int4v *) (lk + kcell*KROW + kch*16) = kst[b];
-            if (v_role) {
-                if (VT) {
-                    *(int2v *) (lv + vrow*VROW + vch*16)     = int2v{ vst[b].x, vst[b].y };
-                    *(int2v *) (lv + vrow*VROW + vch*16 + 8) = int2v{ vst[b].z, vst[b].w };
-                } else {        // transpose on the way in: 8 dims of one cell -> 8 rows of V^T
-                    const uint32_t w[4] = { (uint32_t) vst[b].x, (uint32_t) vst[b].y, (uint32_t) vst[b].z, (uint32_t) vst[b].w };
 #pragma unroll
-                    for (int e = 0; e < 8; e++) *(uint16_t *) (lv + (kch*8 + e)*VROW + kcell*2) = (uint16_t)(w[e >> 1] >> (16*(e & 1)));
+            for (int r = 0; r < KTR; r++) {
+                const int e = tid + r*NT, kcell = e / CPR, kch = e % CPR;
+                if (e < 32*CPR) *(int4v *) (lk + kcell*KROW + kch*16) = kst[b][r];
+            }
+#pragma unroll
+            for (int r = 0; r < VTR; r++) {
+                const int e = tid + r*NT;
+                if (VT) {
+                    const int vrow = e >> 2, vch = e & 3;
+                    if (e < HDV*4) {
+                        *(int2v *) (lv + vrow*VROW + vch*16)     = int2v{ vst[b][r].x, vst[b][r].y };
+                        *(int2v *) (lv + vrow*VROW + vch*16 + 8) = int2v{ vst[b][r].z, vst[b][r].w };
+                    }
+                } else if (e < 32*CPR) {        // transpose on the way in: 8 dims of one cell -> 8 rows of V^T
+                    const int kcell = e / CPR, kch = e % CPR;
+                    const uint32_t w[4] = { (uint32_t) vst[b][r].x, (uint32_t) vst[b][r].y, (uint32_t) vst[b][r].z, (uint32_t) vst[b][r].w };
+#pragma unroll
+                    for (int i = 0; i < 8; i++) *(uint16_t *) (lv + (kch*8 + i)*VROW + kcell*2) = (uint16_t)(w[i >> 1] >> (16*(i & 1)));
                 }
             }
         }
@@ -254,16 +285,33 @@ __global__ void __launch_bounds__(64*APF_NW) k_attn_prefill(const attn_pf_args p
     }
     const float inv = fin/lt;
     if (q0 + ql < p.T) {
-        float * orow = p.dst ? (float *) ((char *) p.dst + (size_t) t*p.dst_nb1) + (size_t) h*HD : nullptr;
-        uint16_t * yrow = p.y16 ? p.y16 + (size_t) t*p.kp16 + (size_t) h*HD : nullptr;
+        float * orow = p.dst ? (float *) ((char *) p.dst + (size_t) t*p.dst_nb1) + (size_t) h*HDV : nullptr;
+        uint16_t * yrow = p.y16 ? p.y16 + (size_t) t*p.kp16 + (size_t) h*HDV : nullptr;
 #pragma unroll
         for (int d = 0; d < NDT; d++)
 #pragma unroll
             for (int j = 0; j < 4; j++) {
+                if (HDVP != HDV && 32*d + 8*j + 4*hf >= HDV) continue;      // a padded tile's dims
                 const float4v ov = { o[d][4*j]*inv, o[d][4*j + 1]*inv, o[d][4*j + 2]*inv, o[d][4*j + 3]*inv };
                 if (orow) *(float4v *) (orow + 32*d + 8*j + 4*hf) = ov;
                 if (yrow) *(uint2 *) (yrow + 32*d + 8*j + 4*hf) = uint2{ pack_bf16(ov.x, ov.y), pack_bf16(ov.z, ov.w) };
             }
+    }
+}
+
+// One instantiation's launch. LDS: the staging buffers 2*KS*(32*(HDK*2 + 16) + HDVP*72), HDVP = HDV rounded up to 32 — 141 KB at 256 with KS = 2, of a CU's
+// 160 KB; the wave pairs' merge at the end reuses them and is the larger of the two at 80 only: NW/2 receivers x (16*NDT + 2) floats x 64 lanes.
+// KS = 4 exists for the transposed-V form at 128 only (the host never asks for another).
+struct apf_launch_args { const attn_pf_args & a; int hpw; dim3 grid; hipStream_t stream; };
+template <int HD, bool VT, int MK, int KS, int HV, int NW>
+static void apf_launch(const apf_launch_args & l) {
+    if constexpr (KS == 4 && !(HD == 128 && VT)) { fprintf(stderr, "attn_prefill: no four-way form at head size %d\n", HD); abort(); }
+    else {
+        constexpr size_t ndt = (HV + 31)/32, st = (size_t) 2*KS*(32*(HD*2 + APF_KLD) + ndt*32*(64 + 8)), mg = KS > 1 ? (size_t)(NW/2)*(16*ndt + 2)*256 : 0;
+        constexpr size_t lds = st > mg ? st : mg;
+        static_assert(lds <= (size_t) 160*1024, "a workgroup's LDS");
+        MI_LDS_LIMIT_OR_DIE(lds, k_attn_prefill<HD, VT, MK, KS, HV, NW>);
+        hipLaunchKernelGGL((k_attn_prefill<HD, VT, MK, KS, HV, NW>), l.grid, dim3(64*NW), lds, l.stream, l.a, l.hpw);
     }
 }
 
@@ -272,39 +320,47 @@ bool attn_prefill_supported(int64_t head_dim, int64_t n_kv) { return (head_dim =
 void attn_prefill(const void * q, size_t q_nb1, size_t q_nb2, const void * k, size_t k_nb1, size_t k_nb2, const void * v, size_t v_nb1, size_t v_nb2,
                   const void * mask, size_t m_nb1, bool mask_f16, const float * sinks, float * dst, size_t dst_nb1,
                   int64_t head_dim, int64_t n_kv, int64_t n_head, int64_t n_head_kv, int64_t T, float scale, hipStream_t stream, bool v_trans, uint16_t * y16, const attn_extra * ex) {
+    const int64_t hsv = ex && ex->hsv ? ex->hsv : head_dim;
+    if (v_trans ? !attn_fa_head_sizes(head_dim, hsv, T_F16, T_F16) : !(hsv == head_dim && (head_dim == 64 || head_dim == 128))) {
+        fprintf(stderr, "attn_prefill: head sizes (%lld, %lld) have no kernel\n", (long long) head_dim, (long long) hsv); abort();
+    }
     attn_pf_args a = { (const char *) q, q_nb1, q_nb2, (const char *) k, k_nb1, k_nb2, (const char *) v, v_nb1, v_nb2,
-                       (const char *) mask, m_nb1, mask_f16 ? 1 : 0, sinks, dst, dst_nb1, y16, (int)((head_dim*n_head + 63) & ~(int64_t) 63), (int) n_kv, (int) n_head, (int) n_head_kv, (int) T, scale,
+                       (const char *) mask, m_nb1, mask_f16 ? 1 : 0, sinks, dst, dst_nb1, y16, (int)((hsv*n_head + 63) & ~(int64_t) 63), (int) n_kv, (int) n_head, (int) n_head_kv, (int) T, scale,
                        0.0f, 0.0f, 1.0f, 1.0f, 1 };
     if (ex) {
         attn_alibi(ex->max_bias, n_head, a.m0, a.m1, a.n_head_log2);
         a.softcap = ex->softcap; a.max_bias = ex->max_bias;
         if (ex->softcap != 0.0f) a.scale = scale/ex->softcap;
     }
+    const int nw = head_dim > 128 ? 4 : APF_NW;                             // waves per workgroup (the kernel's NW)
     const int64_t R = n_head/n_head_kv;
-    int hpw = R % 8 == 0 ? 8 : R % 4 == 0 ? 4 : R % 2 == 0 ? 2 : 1;          // heads of one kv head per workgroup
+    int hpw = R % 8 == 0 && nw >= 8 ? 8 : R % 4 == 0 ? 4 : R % 2 == 0 ? 2 : 1;          // heads of one kv head per workgroup
     // few workgroups (short prompts): the waves of a (head, query tile) split the cell blocks of an iteration two or four ways, shortening the loop that is the critical path
-    const int64_t wgs1 = ((T + 32*(APF_NW/hpw) - 1)/(32*(APF_NW/hpw)))*(n_head/hpw);
-    int ksp = (hpw <= 4 && wgs1 < 160 && n_kv >= 128) ? 2 : 1;
+    const int64_t wgs1 = ((T + 32*(nw/hpw) - 1)/(32*(nw/hpw)))*(n_head/hpw);
+    int ksp = (hpw*2 <= nw && hpw <= 4 && wgs1 < 160 && n_kv >= 128) ? 2 : 1;
     static const bool ks4_on = env_on("GGML_MI355X_ATTN_PF_KS4");
     if (ks4_on && ksp == 2 && R % 2 == 0 && n_kv >= 256 && head_dim == 128 && v_trans) {
         // ... four ways with two heads per workgroup when even the pairs leave half the chip idle (pp512 of a 32-head model: 128 workgroups -> 256)
         const int64_t wgs2 = ((T + 32*(APF_NW/(hpw*2)) - 1)/(32*(APF_NW/(hpw*2))))*(n_head/hpw);
         if (wgs2 < 200) { hpw = 2; ksp = 4; }
     }
-    const int qpw = APF_NW/(hpw*ksp);                                                // query tiles per workgroup
+    const int qpw = nw/(hpw*ksp);                                                    // query tiles per workgroup
     const dim3 grid((unsigned)((T + 32*qpw - 1)/(32*qpw)), (unsigned)(n_head/hpw));
     const int mk = !mask ? 0 : (mask_f16 ? 2 : 1);
-#define MI_APF2(HD_, VT_, MK_, KS_) do { \
-        constexpr size_t lds_ = (size_t) 2*KS_*(32*(HD_*2 + APF_KLD) + HD_*(64 + 8)); \
-        MI_LDS_LIMIT_OR_DIE(lds_, k_attn_prefill<HD_, VT_, MK_, KS_>); \
-        hipLaunchKernelGGL((k_attn_prefill<HD_, VT_, MK_, KS_>), grid, dim3(64*APF_NW), lds_, stream, a, hpw); } while (0)
-#define MI_APF1(HD_, VT_, MK_) do { if (ksp == 4) { if constexpr (HD_ == 128 && VT_) MI_APF2(HD_, VT_, MK_, 4); } else if (ksp == 2) MI_APF2(HD_, VT_, MK_, 2); else MI_APF2(HD_, VT_, MK_, 1); } while (0)
-#define MI_APF(HD_, VT_) do { if (mk == 0) MI_APF1(HD_, VT_, 0); else if (mk == 1) MI_APF1(HD_, VT_, 1); else MI_APF1(HD_, VT_, 2); } while (0)
-    if (!v_trans) { if (head_dim == 128) MI_APF(128, false); else MI_APF(64, false); }
-    else          { if (head_dim == 128) MI_APF(128, true);  else MI_APF(64, true); }
+    const apf_launch_args la = { a, hpw, grid, stream };
+#define MI_APF1(HD_, VT_, MK_, HV_, NW_) do { if (ksp == 4) apf_launch<HD_, VT_, MK_, 4, HV_, NW_>(la); else if (ksp == 2) apf_launch<HD_, VT_, MK_, 2, HV_, NW_>(la); else apf_launch<HD_, VT_, MK_, 1, HV_, NW_>(la); } while (0)
+#define MI_APF(HD_, VT_, HV_, NW_) do { if (mk == 0) MI_APF1(HD_, VT_, 0, HV_, NW_); else if (mk == 1) MI_APF1(HD_, VT_, 1, HV_, NW_); else MI_APF1(HD_, VT_, 2, HV_, NW_); } while (0)
+    // the (hsk, hsv) pairs of attn_fa_head_sizes, one set of instantiations each
+    if (!v_trans) { if (head_dim == 128) MI_APF(128, false, 128, APF_NW); else MI_APF(64, false, 64, APF_NW); }
+    else if (head_dim == 128) MI_APF(128, true, 128, APF_NW);
+    else if (head_dim == 64)  MI_APF(64, true, 64, APF_NW);
+    else if (head_dim == 80)  MI_APF(80, true, 80, APF_NW);
+    else if (head_dim == 96)  MI_APF(96, true, 96, APF_NW);
+    else if (head_dim == 256) MI_APF(256, true, 256, 4);
+    else if (hsv == 192)      MI_APF(192, true, 192, 4);
+    else                      MI_APF(192, true, 128, 4);
 #undef MI_APF
 #undef MI_APF1
-#undef MI_APF2
 }
 
 // ---- the cache as the kernels above want it: f16, cells as rows or transposed (kv_types.h has the element types) ----
@@ -322,30 +378,31 @@ __global__ void __launch_bounds__(256) k_kv_rows_f16(const kvc_args p) {
     for (int i = 0; i < 4; i++) w[i] = (uint32_t) f32_to_f16_bits(f[2*i]) | ((uint32_t) f32_to_f16_bits(f[2*i + 1]) << 16);
     *(int4v *) (p.dst + ((size_t) hk*p.n_kv + j)*p.hd + sub*8) = int4v{ (int) w[0], (int) w[1], (int) w[2], (int) w[3] };
 }
-// one workgroup = 64 cells of one kv head: cells are read as rows (coalesced), turned in LDS, written as 128-byte pieces of the rows over cells
+// one workgroup = 64 cells of one kv head and a slab of up to 128 dims (blockIdx.z): cells are read as rows (coalesced), turned in LDS, written as 128-byte
+// pieces of the rows over cells
 template <int TY>
 __global__ void __launch_bounds__(256) k_kv_trans_f16(const kvc_args p) {
     constexpr int LROW = 64 + 8;       // halves per LDS row (16-byte aligned rows)
     __shared__ __attribute__((aligned(16))) uint16_t tile[128*LROW];
-    const int hk = blockIdx.y, j0 = blockIdx.x*64, c8 = p.hd >> 3;
+    const int hk = blockIdx.y, j0 = blockIdx.x*64, d0 = blockIdx.z*128, c8 = min(p.hd - d0, 128) >> 3;      // c8: the slab's 8-dim chunks
     for (int e = threadIdx.x; e < 64*c8; e += 256) {
         const int cell = e / c8, sub = e % c8, j = min(j0 + cell, p.n_kv - 1);
         float f[8];
-        kv_cvt8<TY>(kv_raw8<TY>(p.src + (size_t) hk*p.nb2 + (size_t) j*p.nb1, sub), sub, f);
+        kv_cvt8<TY>(kv_raw8<TY>(p.src + (size_t) hk*p.nb2 + (size_t) j*p.nb1, (d0 >> 3) + sub), (d0 >> 3) + sub, f);
 #pragma unroll
         for (int i = 0; i < 8; i++) tile[(sub*8 + i)*LROW + cell] = f32_to_f16_bits(f[i]);
     }
     __syncthreads();
-    for (int e = threadIdx.x; e < p.hd*8; e += 256) {
+    for (int e = threadIdx.x; e < c8*64; e += 256) {
         const int d = e >> 3, g8 = e & 7;
-        if (j0 + g8*8 < p.n_kv) *(int4v *) (p.dst + ((size_t) hk*p.hd + d)*p.n_kv + j0 + g8*8) = *(const int4v *) (tile + d*LROW + g8*8);
+        if (j0 + g8*8 < p.n_kv) *(int4v *) (p.dst + ((size_t) hk*p.hd + d0 + d)*p.n_kv + j0 + g8*8) = *(const int4v *) (tile + d*LROW + g8*8);
     }
 }
 void kv_to_f16(int type, const void * src, size_t nb1, size_t nb2, int64_t hd, int64_t n_kv, int64_t n_head_kv, uint16_t * dst, bool transpose, hipStream_t stream) {
-    if ((hd != 64 && hd != 128) || n_kv % 8 || n_kv < 8) { fprintf(stderr, "kv_to_f16: unsupported shape (hd %lld, n_kv %lld)\n", (long long) hd, (long long) n_kv); abort(); }
+    if (hd % 8 || hd < 8 || hd > 256 || ((type == T_Q8_0 || type == T_Q4_0) && hd % 32) || n_kv % 8 || n_kv < 8) { fprintf(stderr, "kv_to_f16: unsupported shape (hd %lld, n_kv %lld)\n", (long long) hd, (long long) n_kv); abort(); }
     const kvc_args a = { (const char *) src, nb1, nb2, (int) hd, (int) n_kv, (int) n_head_kv, dst };
     const long long tot = (long long) n_head_kv*n_kv*(hd/8);
-#define MI_KVC(TY_) do { if (transpose) hipLaunchKernelGGL((k_kv_trans_f16<TY_>), dim3((unsigned)((n_kv + 63)/64), (unsigned) n_head_kv), dim3(256), 0, stream, a); \
+#define MI_KVC(TY_) do { if (transpose) hipLaunchKernelGGL((k_kv_trans_f16<TY_>), dim3((unsigned)((n_kv + 63)/64), (unsigned) n_head_kv, (unsigned)((hd + 127)/128)), dim3(256), 0, stream, a); \
                          else hipLaunchKernelGGL((k_kv_rows_f16<TY_>), dim3((unsigned)((tot + 255)/256)), dim3(256), 0, stream, a); } while (0)
     if (type == T_F16) MI_KVC(T_F16); else if (type == T_BF16) MI_KVC(T_BF16); else if (type == T_Q8_0) MI_KVC(T_Q8_0); else if (type == T_Q4_0) MI_KVC(T_Q4_0);
     else { fprintf(stderr, "kv_to_f16: cache type %d is not supported\n", type); abort(); }

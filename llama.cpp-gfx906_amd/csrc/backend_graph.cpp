@@ -213,8 +213,8 @@ static enum ggml_status prepare_buffers(mi_backend_ctx * c, const struct ggml_cg
             MI_CHECK_G(hipMemsetAsync(c->fin_cnt, 0, (mi_backend_ctx::FIN_COUNTERS + 8)*4, c->stream)); MI_CHECK_G(hipStreamSynchronize(c->stream));
         } else if (c->fin_img) { (void) hipGetLastError(); (void) hipFree(c->fin_img); c->fin_img = nullptr; c->fin_cnt = nullptr; }
     }
-    if (!c->attn_part) {     // <= 8 tokens x 128 heads x 32 ranges x (128 + 2) floats: allocated once, outside any capture
-        const size_t pb = (size_t) 8*128*32*130*4;
+    if (!c->attn_part) {     // allocated once, outside any capture
+        const size_t pb = ATTN_PART_BYTES;
         if (hipMalloc((void **) &c->attn_part, pb) == hipSuccess) c->attn_part_bytes = pb; else (void) hipGetLastError();
     }
     const size_t need = graph_scratch_need(g);

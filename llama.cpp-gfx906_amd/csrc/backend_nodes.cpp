@@ -44,10 +44,10 @@ void pass_end(mi_backend_ctx * c) {
 // stages with coalesced loads), K when it is not f16; for a few tokens only what the decode kernel does not read directly (attn_decode_kv_types_fused)
 void fa_kv16_plan(const struct ggml_tensor * n, size_t & k_bytes, size_t & v_bytes) {
     const struct ggml_tensor * q = n->src[0]; const struct ggml_tensor * k = n->src[1]; const struct ggml_tensor * v = n->src[2];
-    const size_t dense = (((size_t) k->ne[0]*k->ne[1]*k->ne[2]*2) + 255) & ~(size_t) 255;
-    if (q->ne[1] > 8) { k_bytes = k->type != GGML_TYPE_F16 ? dense : 0; v_bytes = dense; }
+    const size_t k_dense = (((size_t) k->ne[0]*k->ne[1]*k->ne[2]*2) + 255) & ~(size_t) 255, v_dense = (((size_t) v->ne[0]*v->ne[1]*v->ne[2]*2) + 255) & ~(size_t) 255;
+    if (q->ne[1] > 8) { k_bytes = k->type != GGML_TYPE_F16 ? k_dense : 0; v_bytes = v_dense; }
     else if (attn_decode_kv_types_fused((int) k->type, (int) v->type)) { k_bytes = v_bytes = 0; }
-    else { k_bytes = k->type != GGML_TYPE_F16 ? dense : 0; v_bytes = v->type != GGML_TYPE_F16 ? dense : 0; }
+    else { k_bytes = k->type != GGML_TYPE_F16 ? k_dense : 0; v_bytes = v->type != GGML_TYPE_F16 ? v_dense : 0; }
 }
 
 // quantize (or reuse) the activations of a quantized mat-mul: rows r -> x + (r % n_inner)*s_inner + (r / n_inner)*s_outer
@@ -228,13 +228,13 @@ static void op_mul_mat_id(mi_backend_ctx * c, struct ggml_tensor * dst) {
 static void op_flash_attn_ext(mi_backend_ctx * c, struct ggml_tensor * node) {
     const struct ggml_tensor * q = node->src[0]; const struct ggml_tensor * k = node->src[1]; const struct ggml_tensor * v = node->src[2];
     const struct ggml_tensor * mask = node->src[3]; const struct ggml_tensor * sinks = node->src[4];
-    const int64_t hd = k->ne[0], n_kv = k->ne[1], T = q->ne[1];
+    const int64_t hd = k->ne[0], hsv = v->ne[0], n_kv = k->ne[1], T = q->ne[1];      // hd: K's head size
     // what supports_op cannot see (data alignment of the views handed in) fails the graph instead of the process
-    MI_REQUIRE_G(node->nb[1] == (size_t) hd*4 && ((uintptr_t) q->data % 16) == 0);
+    MI_REQUIRE_G(node->nb[1] == (size_t) hsv*4 && ((uintptr_t) q->data % 16) == 0);
     MI_REQUIRE_G(((uintptr_t) k->data % (k->type == GGML_TYPE_F16 || k->type == GGML_TYPE_BF16 ? 16 : 2)) == 0 && ((uintptr_t) v->data % (v->type == GGML_TYPE_F16 || v->type == GGML_TYPE_BF16 ? 16 : 2)) == 0);
     MI_REQUIRE_G(!mask || (mask->ne[0] == n_kv && mask->ne[1] >= T && ((uintptr_t) mask->data % 16) == 0 && mask->nb[1] % 16 == 0));
-    MI_REQUIRE_G(T > 8 || attn_decode_supported(hd, n_kv) || (c->attn_part && attn_decode_supported_split(hd, n_kv) && attn_decode_part_bytes(hd, n_kv, q->ne[2], T) <= c->attn_part_bytes));
-    attn_extra ex = { op_f32(node, 2), op_f32(node, 1), (int) k->type, (int) v->type };
+    MI_REQUIRE_G(attn_fa_supported(hd, hsv, (int) k->type, (int) v->type, n_kv, q->ne[2], T, c->attn_part ? c->attn_part_bytes : 0));
+    attn_extra ex = { op_f32(node, 2), op_f32(node, 1), (int) k->type, (int) v->type, (int) hsv };
     const void * kd = k->data; const void * vd = v->data;
     size_t k_nb1 = k->nb[1], k_nb2 = k->nb[2], v_nb1 = v->nb[1], v_nb2 = v->nb[2];
     size_t kb, vb; fa_kv16_plan(node, kb, vb);
@@ -246,9 +246,9 @@ static void op_flash_attn_ext(mi_backend_ctx * c, struct ggml_tensor * node) {
     }
     if (vb) {
         v_trans = T > 8;
-        kv_to_f16((int) v->type, v->data, v->nb[1], v->nb[2], hd, n_kv, v->ne[2], (uint16_t *) ((char *) c->kv16 + kb), v_trans, c->stream);
+        kv_to_f16((int) v->type, v->data, v->nb[1], v->nb[2], hsv, n_kv, v->ne[2], (uint16_t *) ((char *) c->kv16 + kb), v_trans, c->stream);
         vd = (char *) c->kv16 + kb; ex.v_type = T_F16; c->cnt.kernels_launched++;
-        if (v_trans) { v_nb1 = (size_t) n_kv*2; v_nb2 = (size_t) hd*n_kv*2; } else { v_nb1 = (size_t) hd*2; v_nb2 = (size_t) n_kv*hd*2; }
+        if (v_trans) { v_nb1 = (size_t) n_kv*2; v_nb2 = (size_t) hsv*n_kv*2; } else { v_nb1 = (size_t) hsv*2; v_nb2 = (size_t) n_kv*hsv*2; }
     }
     if (T <= 8) attn_decode(q->data, q->nb[1], q->nb[2], kd, k_nb1, k_nb2, vd, v_nb1, v_nb2, mask ? mask->data : nullptr, mask ? mask->nb[1] : 0, true,
                             sinks ? (const float *) sinks->data : nullptr, (float *) node->data, node->nb[2], hd, n_kv, q->ne[2], k->ne[2], T, op_f32(node, 0), c->stream, false,

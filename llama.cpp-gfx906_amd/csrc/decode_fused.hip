@@ -161,7 +161,7 @@ struct attn_args {
     int n_kv, n_head, n_head_kv, T;
     float scale;
     // long contexts: blockIdx.z splits the cells into nsplit ranges of kv_chunk (a multiple of 32); each workgroup writes its range's
-    // soft_max-weighted V sum (normalised within the range) + its max and denominator to part[(t*n_head + h)*nsplit + z][HD + 2];
+    // soft_max-weighted V sum (normalised within the range) + its max and denominator to part[(t*n_head + h)*nsplit + z][HDV + 2];
     // k_attn_merge combines them (and adds the sink). nsplit = 1: the kernel finishes the row itself.
     int kv_chunk, nsplit; float * part;
     int live_scan;      // row-major V, one workgroup per head: stop at the last unmasked cell
@@ -183,16 +183,39 @@ static __device__ __forceinline__ float dot8_f16_f32(const int4v kv, const float
     return acc;
 }
 
+// flash attention pads the cache view to 256 cells; everything behind the last unmasked cell is dead weight for K, the soft_max and V: find that cell
+// first (one mask value per thread and trip) and walk only up to it (a multiple of 8 cells, at least 8)
+static __device__ __forceinline__ int attn_live_cells(const attn_args & p, int kv_n) {
+    __shared__ int live_w[4];
+    const char * mr = p.mask + (size_t) blockIdx.y*p.m_nb1;
+    int last = -1;
+    for (int j = threadIdx.x; j < kv_n; j += 256) {
+        const float mv = p.mask_f16 ? f16_bits_to_f32(*(const uint16_t *) (mr + (size_t) j*2)) : *(const float *) (mr + (size_t) j*4);
+        if (mv != -INFINITY) last = j;
+    }
+    const float lw = wave_max((float) last);
+    if ((threadIdx.x & 63) == 0) live_w[threadIdx.x >> 6] = (int) lw;
+    __syncthreads();
+    const int lm = max(max(live_w[0], live_w[1]), max(live_w[2], live_w[3]));
+    kv_n = min(kv_n, max(8, (lm + 8) & ~7));
+    __syncthreads();
+    return kv_n;
+}
+
 // Latency is the enemy here (a few hundred KB, one dependent chain per workgroup): every phase issues its independent
 // 16-byte loads in batches of U before touching the data.
 // VT: V is the transposed cache [n_kv, hd] (rows over cells; the graph without flash attention). !VT: V rows are cells [hd, n_kv]
 // (FLASH_ATTN_EXT, src/llama-graph.cpp:1245-1265): v_nb1 is then the cell stride.
 // KQ: the K cache is Q8_0 (-ctk q8_0): a head's row is HD/32 blocks of {f16 d, 32 int8}; a lane's 8 elements are 8 bytes of one block
 // KT / VY: the element types of the K and V rows (kv_types.h). The transposed-V form (VT) takes F16 or Q8_0 K and F16 V only.
-template <int HD, bool VT = true, int KT = T_F16, int VY = T_F16>
+// HD / HDV: the sizes of a K and a V row. The row-major-V form takes every pair of attn_fa_head_sizes; a K row is KCH 16-byte chunks that LPC lanes walk
+// in KR rounds (80 and 96: the lanes past the row's end multiply a clamped chunk by a zero q), a V row DCH chunks with 256 / DCH cells side by side.
+template <int HD, bool VT = true, int KT = T_F16, int VY = T_F16, int HDV = HD>
 __global__ void __launch_bounds__(256) k_attn_decode(const attn_args p) {
     constexpr bool KQ = KT == T_Q8_0;
     static_assert(!VT || ((KT == T_F16 || KT == T_Q8_0) && VY == T_F16), "transposed V: f16 V, f16 or Q8_0 K");
+    static_assert(!VT || (HDV == HD && (HD == 64 || HD == 128)), "transposed V: head size 64 / 128");
+    static_assert(HD % 8 == 0 && HDV % 8 == 0 && HDV <= 256, "rows of 16-byte chunks; one thread per output dim");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float * s = (float *) smem;                          // [n_kv] scores -> probabilities
     __shared__ float sh[4];
@@ -202,32 +225,6 @@ __global__ void __launch_bounds__(256) k_attn_decode(const attn_args p) {
     const int kv_lo = split ? (int) blockIdx.z*p.kv_chunk : 0;
     int kv_n = split ? min(p.n_kv - kv_lo, p.kv_chunk) : p.n_kv;   // this workgroup's cells
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    constexpr int LPC = HD/8;                            // lanes per K row (8 f16 = 16 B each)
-    constexpr int CPW = 64/LPC;                          // K rows per wave step
-    constexpr int U = 4;
-    const int sub = lane % LPC, cw = lane / LPC;
-    // q: written by the launch before on other XCDs, i.e. the longest wait of this launch — asked for before anything else (the live scan below waits for the mask)
-    const float * qp = (const float *) (p.q + (size_t) t*p.q_nb1 + (size_t) h*p.q_nb2) + sub*8;
-    const float4v q0_ld = *(const float4v *) qp, q1_ld = *(const float4v *) (qp + 4);
-    if (!VT && !split && p.live_scan && p.mask) {
-        // flash attention pads the cache view to 256 cells; everything behind the last unmasked cell is dead weight for K, the soft_max and V: find that cell
-        // first (one mask value per thread and trip) and walk only up to it (a multiple of 8 cells, at least 8)
-        __shared__ int live_w[4];
-        const char * mr = p.mask + (size_t) blockIdx.y*p.m_nb1;
-        int last = -1;
-        for (int j = threadIdx.x; j < kv_n; j += 256) {
-            const float mv = p.mask_f16 ? f16_bits_to_f32(*(const uint16_t *) (mr + (size_t) j*2)) : *(const float *) (mr + (size_t) j*4);
-            if (mv != -INFINITY) last = j;
-        }
-        const float lw = wave_max((float) last);
-        if ((threadIdx.x & 63) == 0) live_w[threadIdx.x >> 6] = (int) lw;
-        __syncthreads();
-        const int lm = max(max(live_w[0], live_w[1]), max(live_w[2], live_w[3]));
-        kv_n = min(kv_n, max(8, (lm + 8) & ~7));
-        __syncthreads();
-    }
-
-    // ---- scores: s[j] = scale * K[j].q + mask[j] ----
     if (!KQ) {
         // the no-flash-attention graph's K.q is MUL_MAT(F16 cache, F32 q): the CPU backend converts q to the F16 operand type first (vec_dot_type of
         // F16, tests/test-quantize-fns.cpp:82-99) — followed here, so that the logits match the CPU reference and not just the exact product
@@ -237,65 +234,163 @@ __global__ void __launch_bounds__(256) k_attn_decode(const attn_args p) {
         // only asked for after q had arrived: two memory round trips in a row on a 5 us launch)
 #define MI_R16(x_) x_ = f16_bits_to_f32(f32_to_f16_bits(x_))
     }
-    const char * kbase = p.k + (size_t) hk*p.k_nb2 + (KT == T_F16 ? sub*16 : KQ ? (sub >> 2)*34 : 0) + (size_t) kv_lo*p.k_nb1;
-    const bool alibi = p.max_bias > 0.0f;
-    const float slope = attn_slope(p.max_bias, p.m0, p.m1, p.n_head_log2, h);
-    const char * mrow = p.mask ? p.mask + (size_t) t*p.m_nb1 + (size_t) kv_lo*(p.mask_f16 ? 2 : 4) : nullptr;
-    // transposed V: the first 128 cells' worth of every lane's V rows is requested NOW, next to q and K — the soft_max in between does
-    // not need them and the loads do not need the soft_max (one memory round trip less on the chain for n_kv <= 128: tg128)
     constexpr int NGP = VT ? HD/16 : 1;
     int4v vpre[NGP];
-    if (VT) {
-        const int l16p = lane & 15, rwp = lane >> 4;
-        const char * vb0 = p.v + (size_t) hk*p.v_nb2 + (size_t)(wave*4 + rwp)*p.v_nb1 + (size_t) kv_lo*2;
-        const int c0 = min(l16p, max((kv_n >> 3) - 1, 0));
+    float mx;
+    constexpr int U = 4;
+    // ---- scores: s[j] = scale * K[j].q + mask[j]. Head sizes 64 / 128 (a lane owns one 16-byte chunk of a K row): the kernel as it has always been, so that
+    //      these instantiations stay what they were; the other sizes walk KR chunks per lane ----
+    if constexpr (HD == 64 || HD == 128) {
+        constexpr int LPC = HD/8;                            // lanes per K row (8 f16 = 16 B each)
+        constexpr int CPW = 64/LPC;                          // K rows per wave step
+        const int sub = lane % LPC, cw = lane / LPC;
+        // q: written by the launch before on other XCDs, i.e. the longest wait of this launch — asked for before anything else (the live scan below waits for the mask)
+        const float * qp = (const float *) (p.q + (size_t) t*p.q_nb1 + (size_t) h*p.q_nb2) + sub*8;
+        const float4v q0_ld = *(const float4v *) qp, q1_ld = *(const float4v *) (qp + 4);
+        if (!VT && !split && p.live_scan && p.mask) kv_n = attn_live_cells(p, kv_n);
+
+        // ---- scores: s[j] = scale * K[j].q + mask[j] ----
+        const char * kbase = p.k + (size_t) hk*p.k_nb2 + (KT == T_F16 ? sub*16 : KQ ? (sub >> 2)*34 : 0) + (size_t) kv_lo*p.k_nb1;
+        const bool alibi = p.max_bias > 0.0f;
+        const float slope = attn_slope(p.max_bias, p.m0, p.m1, p.n_head_log2, h);
+        const char * mrow = p.mask ? p.mask + (size_t) t*p.m_nb1 + (size_t) kv_lo*(p.mask_f16 ? 2 : 4) : nullptr;
+        // transposed V: the first 128 cells' worth of every lane's V rows is requested NOW, next to q and K — the soft_max in between does
+        // not need them and the loads do not need the soft_max (one memory round trip less on the chain for n_kv <= 128: tg128)
+        if (VT) {
+            const int l16p = lane & 15, rwp = lane >> 4;
+            const char * vb0 = p.v + (size_t) hk*p.v_nb2 + (size_t)(wave*4 + rwp)*p.v_nb1 + (size_t) kv_lo*2;
+            const int c0 = min(l16p, max((kv_n >> 3) - 1, 0));
 #pragma unroll
-        for (int g = 0; g < NGP; g++) vpre[g] = ld_b128(vb0 + (size_t)(g*16)*p.v_nb1 + (size_t) c0*16);
-    }
-    float mx = (p.sinks && !split) ? p.sinks[h] : -INFINITY;
-    for (int j0 = wave*CPW + cw; j0 < kv_n; j0 += 4*CPW*U) {
-        int4v kreg[U]; float mreg[U]; uint32_t mraw[U];
-#pragma unroll
-        for (int u = 0; u < U; u++) {
-            const int j = min(j0 + u*4*CPW, kv_n - 1);
-            if (KQ) {     // .x, .y: the lane's 8 quants; .z: the block's scale (blocks are 34 bytes: 2-byte aligned loads)
-                const int2v qq = ld_b64(kbase + (size_t) j*p.k_nb1 + 2 + (sub & 3)*8);
-                kreg[u] = int4v{ qq.x, qq.y, (int) ld_u16(kbase + (size_t) j*p.k_nb1), 0 };
-            } else if (KT == T_F16)
-            kreg[u] = *(const int4v *) (kbase + (size_t) j*p.k_nb1);
-            else kreg[u] = kv_raw8<KT>(kbase + (size_t) j*p.k_nb1, sub);
-            // (the mask value is only REQUESTED here — raw bits, converted below: converting an f16 mask value on the spot put a wait for every outstanding load
-            // behind each of the U row requests, one memory round trip per cell instead of one per batch: ISA of the -fa 1 form)
-            mraw[u] = 0;
-            if (mrow) { if (p.mask_f16) mraw[u] = *(const uint16_t *) (mrow + (size_t) j*2); else mraw[u] = *(const uint32_t *) (mrow + (size_t) j*4); }
+            for (int g = 0; g < NGP; g++) vpre[g] = ld_b128(vb0 + (size_t)(g*16)*p.v_nb1 + (size_t) c0*16);
         }
+        mx = (p.sinks && !split) ? p.sinks[h] : -INFINITY;
+        for (int j0 = wave*CPW + cw; j0 < kv_n; j0 += 4*CPW*U) {
+            int4v kreg[U]; float mreg[U]; uint32_t mraw[U];
 #pragma unroll
-        for (int u = 0; u < U; u++) mreg[u] = !mrow ? 0.0f : p.mask_f16 ? f16_bits_to_f32((uint16_t) mraw[u]) : __builtin_bit_cast(float, mraw[u]);
-        float4v q0 = q0_ld, q1 = q1_ld;
-        asm volatile("" : "+v"(q0), "+v"(q1));      // (opaque: the conversion below is loop-invariant and would be hoisted back in front of the K requests)
-        if (!KQ) { MI_R16(q0.x); MI_R16(q0.y); MI_R16(q0.z); MI_R16(q0.w); MI_R16(q1.x); MI_R16(q1.y); MI_R16(q1.z); MI_R16(q1.w); }
-#pragma unroll
-        for (int u = 0; u < U; u++) {
-            const int j = j0 + u*4*CPW;
-            float acc;
-            if (KQ) {
-                const int a0 = kreg[u].x, a1 = kreg[u].y;
-                acc = ((float)(int8_t) a0*q0.x + (float)(int8_t)(a0 >> 8)*q0.y) + ((float)(int8_t)(a0 >> 16)*q0.z + (float)(a0 >> 24)*q0.w)
-                    + ((float)(int8_t) a1*q1.x + (float)(int8_t)(a1 >> 8)*q1.y) + ((float)(int8_t)(a1 >> 16)*q1.z + (float)(a1 >> 24)*q1.w);
-                acc *= f16_bits_to_f32((uint16_t) kreg[u].z);
-            } else if (KT == T_F16) acc = dot8_f16_f32(kreg[u], q0, q1);
-            else {
-                float f[8]; kv_cvt8<KT>(kreg[u], sub, f);
-                acc  = f[0]*q0.x + f[1]*q0.y; acc += f[2]*q0.z + f[3]*q0.w; acc += f[4]*q1.x + f[5]*q1.y; acc += f[6]*q1.z + f[7]*q1.w;
+            for (int u = 0; u < U; u++) {
+                const int j = min(j0 + u*4*CPW, kv_n - 1);
+                if (KQ) {     // .x, .y: the lane's 8 quants; .z: the block's scale (blocks are 34 bytes: 2-byte aligned loads)
+                    const int2v qq = ld_b64(kbase + (size_t) j*p.k_nb1 + 2 + (sub & 3)*8);
+                    kreg[u] = int4v{ qq.x, qq.y, (int) ld_u16(kbase + (size_t) j*p.k_nb1), 0 };
+                } else if (KT == T_F16)
+                kreg[u] = *(const int4v *) (kbase + (size_t) j*p.k_nb1);
+                else kreg[u] = kv_raw8<KT>(kbase + (size_t) j*p.k_nb1, sub);
+                // (the mask value is only REQUESTED here — raw bits, converted below: converting an f16 mask value on the spot put a wait for every outstanding load
+                // behind each of the U row requests, one memory round trip per cell instead of one per batch: ISA of the -fa 1 form)
+                mraw[u] = 0;
+                if (mrow) { if (p.mask_f16) mraw[u] = *(const uint16_t *) (mrow + (size_t) j*2); else mraw[u] = *(const uint32_t *) (mrow + (size_t) j*4); }
             }
-            acc += dpp_f<0xB1>(acc); acc += dpp_f<0x4E>(acc); acc += dpp_f<0x141>(acc);   // sum over the LPC lanes of the row
-            if (LPC == 16) acc += dpp_f<0x140>(acc);
-            if (j < kv_n) {
-                float v;
-                if (p.softcap != 0.0f || alibi) { v = acc*p.scale; if (p.softcap != 0.0f) v = p.softcap*tanhf(v); v += slope*mreg[u]; }
-                else v = acc*p.scale + mreg[u];
-                if (sub == 0) s[j] = v;
-                mx = fmaxf(mx, v);
+#pragma unroll
+            for (int u = 0; u < U; u++) mreg[u] = !mrow ? 0.0f : p.mask_f16 ? f16_bits_to_f32((uint16_t) mraw[u]) : __builtin_bit_cast(float, mraw[u]);
+            float4v q0 = q0_ld, q1 = q1_ld;
+            asm volatile("" : "+v"(q0), "+v"(q1));      // (opaque: the conversion below is loop-invariant and would be hoisted back in front of the K requests)
+            if (!KQ) { MI_R16(q0.x); MI_R16(q0.y); MI_R16(q0.z); MI_R16(q0.w); MI_R16(q1.x); MI_R16(q1.y); MI_R16(q1.z); MI_R16(q1.w); }
+#pragma unroll
+            for (int u = 0; u < U; u++) {
+                const int j = j0 + u*4*CPW;
+                float acc;
+                if (KQ) {
+                    const int a0 = kreg[u].x, a1 = kreg[u].y;
+                    acc = ((float)(int8_t) a0*q0.x + (float)(int8_t)(a0 >> 8)*q0.y) + ((float)(int8_t)(a0 >> 16)*q0.z + (float)(a0 >> 24)*q0.w)
+                        + ((float)(int8_t) a1*q1.x + (float)(int8_t)(a1 >> 8)*q1.y) + ((float)(int8_t)(a1 >> 16)*q1.z + (float)(a1 >> 24)*q1.w);
+                    acc *= f16_bits_to_f32((uint16_t) kreg[u].z);
+                } else if (KT == T_F16) acc = dot8_f16_f32(kreg[u], q0, q1);
+                else {
+                    float f[8]; kv_cvt8<KT>(kreg[u], sub, f);
+                    acc  = f[0]*q0.x + f[1]*q0.y; acc += f[2]*q0.z + f[3]*q0.w; acc += f[4]*q1.x + f[5]*q1.y; acc += f[6]*q1.z + f[7]*q1.w;
+                }
+                acc += dpp_f<0xB1>(acc); acc += dpp_f<0x4E>(acc); acc += dpp_f<0x141>(acc);   // sum over the LPC lanes of the row
+                if (LPC == 16) acc += dpp_f<0x140>(acc);
+                if (j < kv_n) {
+                    float v;
+                    if (p.softcap != 0.0f || alibi) { v = acc*p.scale; if (p.softcap != 0.0f) v = p.softcap*tanhf(v); v += slope*mreg[u]; }
+                    else v = acc*p.scale + mreg[u];
+                    if (sub == 0) s[j] = v;
+                    mx = fmaxf(mx, v);
+                }
+            }
+        }
+    } else {      // (row-major V only: the transposed-V form stops at 64 / 128)
+        static_assert(!VT, "the walked K row is the flash-attention form's");
+        constexpr int KCH = HD/8;                            // 16-byte chunks (8 elements) of a K row
+        constexpr int LPC = HD == 192 ? 8 : 16;              // lanes per K row (192: 3 x 8 chunks; 80, 96, 256: 16 lanes)
+        constexpr int KR = (KCH + LPC - 1)/LPC;              // chunks a lane walks: one to three
+        constexpr bool KFULL = KCH % LPC == 0;               // no lane past the end of the row
+        constexpr int CPW = 64/LPC;                          // K rows per wave step
+        const int sub = lane % LPC, cw = lane / LPC;
+        // q: written by the launch before on other XCDs, i.e. the longest wait of this launch — asked for before anything else (the live scan below waits for the mask)
+        float4v q0_ld[KR], q1_ld[KR];
+        int kc[KR];                                          // the lane's chunks, clamped to the row
+#pragma unroll
+        for (int r = 0; r < KR; r++) {
+            kc[r] = KFULL ? sub + r*LPC : min(sub + r*LPC, KCH - 1);
+            const float * qp = (const float *) (p.q + (size_t) t*p.q_nb1 + (size_t) h*p.q_nb2) + kc[r]*8;
+            q0_ld[r] = *(const float4v *) qp; q1_ld[r] = *(const float4v *) (qp + 4);
+            if (!KFULL && sub + r*LPC >= KCH) { q0_ld[r] = float4v{ 0.0f, 0.0f, 0.0f, 0.0f }; q1_ld[r] = q0_ld[r]; }
+        }
+        if (!split && p.live_scan && p.mask) kv_n = attn_live_cells(p, kv_n);
+
+        const char * kbase = p.k + (size_t) hk*p.k_nb2 + (KT == T_F16 ? kc[0]*16 : KQ ? (kc[0] >> 2)*34 : 0) + (size_t) kv_lo*p.k_nb1;      // the lane's first chunk
+        const char * krow = p.k + (size_t) hk*p.k_nb2 + (size_t) kv_lo*p.k_nb1;                                                               // the row (further chunks)
+        const bool alibi = p.max_bias > 0.0f;
+        const float slope = attn_slope(p.max_bias, p.m0, p.m1, p.n_head_log2, h);
+        const char * mrow = p.mask ? p.mask + (size_t) t*p.m_nb1 + (size_t) kv_lo*(p.mask_f16 ? 2 : 4) : nullptr;
+        mx = (p.sinks && !split) ? p.sinks[h] : -INFINITY;
+        for (int j0 = wave*CPW + cw; j0 < kv_n; j0 += 4*CPW*U) {
+            int4v kreg[U][KR]; float mreg[U]; uint32_t mraw[U];
+#pragma unroll
+            for (int u = 0; u < U; u++) {
+                const int j = min(j0 + u*4*CPW, kv_n - 1);
+                if (KQ) {     // .x, .y: the lane's 8 quants; .z: the block's scale (blocks are 34 bytes: 2-byte aligned loads)
+                    const int2v qq = ld_b64(kbase + (size_t) j*p.k_nb1 + 2 + (kc[0] & 3)*8);
+                    kreg[u][0] = int4v{ qq.x, qq.y, (int) ld_u16(kbase + (size_t) j*p.k_nb1), 0 };
+                } else if (KT == T_F16)
+                kreg[u][0] = *(const int4v *) (kbase + (size_t) j*p.k_nb1);
+                else kreg[u][0] = kv_raw8<KT>(kbase + (size_t) j*p.k_nb1, kc[0]);
+#pragma unroll
+                for (int r = 1; r < KR; r++) kreg[u][r] = kv_raw8<KT>(krow + (size_t) j*p.k_nb1, kc[r]);
+                // (the mask value is only REQUESTED here — raw bits, converted below: converting an f16 mask value on the spot put a wait for every outstanding load
+                // behind each of the U row requests, one memory round trip per cell instead of one per batch: ISA of the -fa 1 form)
+                mraw[u] = 0;
+                if (mrow) { if (p.mask_f16) mraw[u] = *(const uint16_t *) (mrow + (size_t) j*2); else mraw[u] = *(const uint32_t *) (mrow + (size_t) j*4); }
+            }
+#pragma unroll
+            for (int u = 0; u < U; u++) mreg[u] = !mrow ? 0.0f : p.mask_f16 ? f16_bits_to_f32((uint16_t) mraw[u]) : __builtin_bit_cast(float, mraw[u]);
+            float4v q0[KR], q1[KR];
+#pragma unroll
+            for (int r = 0; r < KR; r++) {
+                q0[r] = q0_ld[r]; q1[r] = q1_ld[r];
+                asm volatile("" : "+v"(q0[r]), "+v"(q1[r]));      // (opaque: the conversion below is loop-invariant and would be hoisted back in front of the K requests)
+                if (!KQ) { MI_R16(q0[r].x); MI_R16(q0[r].y); MI_R16(q0[r].z); MI_R16(q0[r].w); MI_R16(q1[r].x); MI_R16(q1[r].y); MI_R16(q1[r].z); MI_R16(q1[r].w); }
+            }
+#pragma unroll
+            for (int u = 0; u < U; u++) {
+                const int j = j0 + u*4*CPW;
+                float acc;
+#pragma unroll
+                for (int r = 0; r < KR; r++) {
+                    float ar;
+                    if (KQ) {
+                        const int a0 = kreg[u][r].x, a1 = kreg[u][r].y;
+                        ar = ((float)(int8_t) a0*q0[r].x + (float)(int8_t)(a0 >> 8)*q0[r].y) + ((float)(int8_t)(a0 >> 16)*q0[r].z + (float)(a0 >> 24)*q0[r].w)
+                           + ((float)(int8_t) a1*q1[r].x + (float)(int8_t)(a1 >> 8)*q1[r].y) + ((float)(int8_t)(a1 >> 16)*q1[r].z + (float)(a1 >> 24)*q1[r].w);
+                        ar *= f16_bits_to_f32((uint16_t) kreg[u][r].z);
+                    } else if (KT == T_F16) ar = dot8_f16_f32(kreg[u][r], q0[r], q1[r]);
+                    else {
+                        float f[8]; kv_cvt8<KT>(kreg[u][r], kc[r], f);
+                        ar  = f[0]*q0[r].x + f[1]*q0[r].y; ar += f[2]*q0[r].z + f[3]*q0[r].w; ar += f[4]*q1[r].x + f[5]*q1[r].y; ar += f[6]*q1[r].z + f[7]*q1[r].w;
+                    }
+                    acc = r == 0 ? ar : acc + ar;
+                }
+                acc += dpp_f<0xB1>(acc); acc += dpp_f<0x4E>(acc); acc += dpp_f<0x141>(acc);   // sum over the LPC lanes of the row
+                if (LPC == 16) acc += dpp_f<0x140>(acc);
+                if (j < kv_n) {
+                    float v;
+                    if (p.softcap != 0.0f || alibi) { v = acc*p.scale; if (p.softcap != 0.0f) v = p.softcap*tanhf(v); v += slope*mreg[u]; }
+                    else v = acc*p.scale + mreg[u];
+                    if (sub == 0) s[j] = v;
+                    mx = fmaxf(mx, v);
+                }
             }
         }
     }
@@ -317,17 +412,18 @@ __global__ void __launch_bounds__(256) k_attn_decode(const attn_args p) {
     else for (int j = threadIdx.x; j < kv_n; j += 256) s[j] *= inv;
     __syncthreads();
     // where the result goes: the output row, or this range's slot of the partial buffer (+ its max and denominator)
-    float * orow = split ? p.part + ((size_t)(t*p.n_head + h)*p.nsplit + blockIdx.z)*(HD + 2) : (float *) ((char *) p.dst + (size_t) t*p.dst_nb1) + (size_t) h*HD;
-    if (split && threadIdx.x == 0) { orow[HD] = mx; orow[HD + 1] = sum; }
+    float * orow = split ? p.part + ((size_t)(t*p.n_head + h)*p.nsplit + blockIdx.z)*(HDV + 2) : (float *) ((char *) p.dst + (size_t) t*p.dst_nb1) + (size_t) h*HDV;
+    if (split && threadIdx.x == 0) { orow[HDV] = mx; orow[HDV + 1] = sum; }
 
     if (!VT) {
         // ---- out[d] = sum_j p[j]*V[j][d]: a thread owns 8 dims of every NGR-th cell; partial sums meet in LDS ----
-        constexpr int DCH = HD/8, NGR = 256/DCH, UV = 4;
-        float * red = (float *) (smem + (((size_t)(split ? p.kv_chunk : p.n_kv)*4 + 15) & ~(size_t) 15));     // [NGR][HD]
+        constexpr int DCH = HDV/8, NGR = 256/DCH, UV = 4;      // (80, 96, 192: the 256 - NGR*DCH threads left over idle)
+        float * red = (float *) (smem + (((size_t)(split ? p.kv_chunk : p.n_kv)*4 + 15) & ~(size_t) 15));     // [NGR][HDV]: attn_red_bytes
         const int dch = threadIdx.x % DCH, cg = threadIdx.x / DCH;
+        const bool vact = 256 % DCH == 0 || cg < NGR;
         const char * vb = p.v + (size_t) hk*p.v_nb2 + (VY == T_F16 ? (size_t) dch*16 : 0) + (size_t) kv_lo*p.v_nb1;
         float a8[8] = { 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f };
-        for (int j0 = cg; j0 < kv_n; j0 += NGR*UV) {
+        for (int j0 = vact ? cg : kv_n; j0 < kv_n; j0 += NGR*UV) {
             int4v vr[UV]; float pj[UV];
 #pragma unroll
             for (int u = 0; u < UV; u++) {
@@ -352,11 +448,11 @@ __global__ void __launch_bounds__(256) k_attn_decode(const attn_args p) {
             }
         }
 #pragma unroll
-        for (int i = 0; i < 8; i++) red[cg*HD + dch*8 + i] = a8[i];
+        for (int i = 0; i < 8; i++) if (vact) red[cg*HDV + dch*8 + i] = a8[i];
         __syncthreads();
-        if (threadIdx.x < HD) {
+        if (threadIdx.x < HDV) {
             float r = 0.0f;
-            for (int gq = 0; gq < NGR; gq++) r += red[gq*HD + threadIdx.x];
+            for (int gq = 0; gq < NGR; gq++) r += red[gq*HDV + threadIdx.x];
             orow[threadIdx.x] = r;
         }
         return;
@@ -385,7 +481,7 @@ __global__ void __launch_bounds__(256) k_attn_decode(const attn_args p) {
 }
 
 // combine the cell ranges of one (token, head): out = sum_i w_i o_i / (sum_i w_i [+ e^(sink - M)]), w_i = l_i e^(m_i - M), M = max(m_i [, sink])
-template <int HD>
+template <int HD>      // V's head size
 __global__ void __launch_bounds__(HD) k_attn_merge(const attn_args p) {
     const int h = blockIdx.x, t = blockIdx.y, d = threadIdx.x;
     const float * pr = p.part + (size_t)(t*p.n_head + h)*p.nsplit*(HD + 2);
@@ -401,17 +497,35 @@ __global__ void __launch_bounds__(HD) k_attn_merge(const attn_args p) {
 }
 
 // without a partial buffer the whole row of scores must fit the workgroup's LDS
-bool attn_decode_supported(int64_t head_dim, int64_t n_kv) { return (head_dim == 128 || head_dim == 64) && n_kv % 8 == 0 && n_kv*4 <= 48*1024; }
+static bool attn_one_wg_shape(int64_t n_kv) { return n_kv % 8 == 0 && n_kv*4 <= 48*1024; }
+bool attn_decode_supported(int64_t head_dim, int64_t n_kv) { return (head_dim == 128 || head_dim == 64) && attn_one_wg_shape(n_kv); }
 // measured (tg1024 / --fa 1 tg128): the transposed-V kernel gains from 384-512 cells on, the row-V (flash attention) one already at 256
 static int64_t attn_split_min(bool v_trans = true) {
     static const int64_t v = env_int("GGML_MI355X_ATTN_SPLIT_MIN", 0);
     return v ? (v < 256 ? 256 : v) : (v_trans ? 384 : 256);
 }
-bool attn_decode_supported_split(int64_t head_dim, int64_t n_kv) { return (head_dim == 128 || head_dim == 64) && n_kv >= attn_split_min(true) && n_kv % 32 == 0; }
-size_t attn_decode_part_bytes(int64_t head_dim, int64_t n_kv, int64_t n_head, int64_t T) {     // 0: no split for this shape
+static bool attn_split_shape(int64_t n_kv) { return n_kv >= attn_split_min(true) && n_kv % 32 == 0; }
+bool attn_decode_supported_split(int64_t head_dim, int64_t n_kv) { return (head_dim == 128 || head_dim == 64) && attn_split_shape(n_kv); }
+size_t attn_decode_part_bytes(int64_t hsv, int64_t n_kv, int64_t n_head, int64_t T) {     // 0: no split for this shape
     if (n_kv < attn_split_min(false) || n_kv % 32 != 0) return 0;
     const int64_t ns = (n_kv + 127)/128 < 32 ? (n_kv + 127)/128 : 32;
-    return (size_t) T*n_head*ns*(head_dim + 2)*4;
+    return (size_t) T*n_head*ns*(hsv + 2)*4;
+}
+// the row-major-V kernel's [256/(hsv/8)][hsv] partial sums behind the scores
+static size_t attn_red_bytes(int64_t hsv) { return (size_t)(256/(hsv/8))*hsv*4; }
+
+// FLASH_ATTN_EXT: the (K, V) head sizes with a kernel. 80 is not a multiple of a 32-element block: F16 / BF16 caches only (the host pads a quantized cache to 96).
+bool attn_fa_head_sizes(int64_t hsk, int64_t hsv, int k_type, int v_type) {
+    if (hsk == 192 && hsv == 128) return true;
+    if (hsk != hsv) return false;
+    if (hsk == 80) return (k_type == T_F16 || k_type == T_BF16) && (v_type == T_F16 || v_type == T_BF16);
+    return hsk == 64 || hsk == 96 || hsk == 128 || hsk == 192 || hsk == 256;
+}
+bool attn_fa_supported(int64_t hsk, int64_t hsv, int k_type, int v_type, int64_t n_kv, int64_t n_head, int64_t T, size_t part_bytes) {
+    if (!attn_fa_head_sizes(hsk, hsv, k_type, v_type)) return false;
+    if (T > 8) return n_kv % 32 == 0 && n_kv > 0;
+    // few tokens: the whole score row in LDS, or the cell ranges through the partial-result buffer
+    return attn_one_wg_shape(n_kv) || (attn_split_shape(n_kv) && attn_decode_part_bytes(hsv, n_kv, n_head, T) <= part_bytes);
 }
 
 // which (K, V) type pairs the row-major-V (flash attention) kernel reads directly; the others go through kv_to_f16 first
@@ -440,10 +554,14 @@ void attn_decode(const void * q, size_t q_nb1, size_t q_nb2, const void * k, siz
         if (ex->v_type) vy = ex->v_type;
     }
     if (v_trans ? !((kt == T_F16 || kt == T_Q8_0) && vy == T_F16) : !attn_decode_kv_types_fused(kt, vy)) { fprintf(stderr, "attn_decode: KV types (%d, %d) have no kernel\n", kt, vy); abort(); }
+    const int64_t hsv = ex && ex->hsv ? ex->hsv : head_dim;
+    if (v_trans ? !(hsv == head_dim && (head_dim == 64 || head_dim == 128)) : !attn_fa_head_sizes(head_dim, hsv, kt, vy)) {
+        fprintf(stderr, "attn_decode: head sizes (%lld, %lld) have no kernel\n", (long long) head_dim, (long long) hsv); abort();
+    }
     // long contexts: one workgroup per (head, token) walks every cell alone — 32 workgroups on 256 CUs. With a partial buffer the cells
     // are split into ranges of >= 256 (at most 32 ranges) that run side by side and a small second kernel merges them.
     static const bool split_on = env_on("GGML_MI355X_ATTN_SPLIT");
-    const size_t need = attn_decode_part_bytes(head_dim, n_kv, n_head, T);
+    const size_t need = attn_decode_part_bytes(hsv, n_kv, n_head, T);
     // row-major V (flash attention) at exactly the padding size: most cells of a short context are masked padding — one workgroup per head that stops at the last
     // live cell beats two ranges + a merge launch there (GGML_MI355X_ATTN_LIVE_SCAN=0: the split as before)
     static const bool live_on = env_on("GGML_MI355X_ATTN_LIVE_SCAN");
@@ -456,17 +574,26 @@ void attn_decode(const void * q, size_t q_nb1, size_t q_nb2, const void * k, siz
         a.kv_chunk = (int) chunk; a.nsplit = (int) ns; a.part = part;
     }
     const dim3 grid((unsigned) n_head, (unsigned) T, (unsigned) a.nsplit);
-    const size_t lds = (((size_t)(a.nsplit > 1 ? a.kv_chunk : n_kv)*4 + 15) & ~(size_t) 15) + (v_trans ? 0 : 8192);     // !v_trans: + [256/(hd/8)][hd] partial sums
+    const size_t lds = (((size_t)(a.nsplit > 1 ? a.kv_chunk : n_kv)*4 + 15) & ~(size_t) 15) + (v_trans ? 0 : attn_red_bytes(hsv));
+    if (lds > 64*1024) { fprintf(stderr, "attn_decode: %zu bytes of LDS for n_kv %lld\n", lds, (long long) n_kv); abort(); }      // (shapes attn_fa_supported / attn_decode_supported turn away)
     if (!v_trans) {
-#define MI_AD(KT_, VY_) do { if (head_dim == 128) hipLaunchKernelGGL((k_attn_decode<128, false, KT_, VY_>), grid, dim3(256), lds, stream, a); \
-                             else                 hipLaunchKernelGGL((k_attn_decode<64, false, KT_, VY_>),  grid, dim3(256), lds, stream, a); } while (0)
-        if (kt == T_F16 && vy == T_F16)        MI_AD(T_F16, T_F16);
+        // the (hsk, hsv) pairs of attn_fa_head_sizes, one instantiation each; 80: F16 / BF16 only
+#define MI_AD1(HK_, HV_, KT_, VY_) hipLaunchKernelGGL((k_attn_decode<HK_, false, KT_, VY_, HV_>), grid, dim3(256), lds, stream, a)
+#define MI_AD(KT_, VY_) do { if (head_dim == 128)      MI_AD1(128, 128, KT_, VY_); \
+                             else if (head_dim == 64)  MI_AD1(64, 64, KT_, VY_); \
+                             else if (head_dim == 96)  MI_AD1(96, 96, KT_, VY_); \
+                             else if (head_dim == 256) MI_AD1(256, 256, KT_, VY_); \
+                             else if (hsv == 192)      MI_AD1(192, 192, KT_, VY_); \
+                             else                      MI_AD1(192, 128, KT_, VY_); } while (0)
+        if (head_dim == 80) { if (kt == T_F16) MI_AD1(80, 80, T_F16, T_F16); else MI_AD1(80, 80, T_BF16, T_BF16); }
+        else if (kt == T_F16 && vy == T_F16)   MI_AD(T_F16, T_F16);
         else if (kt == T_Q8_0 && vy == T_Q8_0) MI_AD(T_Q8_0, T_Q8_0);
         else if (kt == T_Q4_0 && vy == T_Q4_0) MI_AD(T_Q4_0, T_Q4_0);
         else if (kt == T_BF16 && vy == T_BF16) MI_AD(T_BF16, T_BF16);
         else if (kt == T_Q8_0 && vy == T_F16)  MI_AD(T_Q8_0, T_F16);
         else                                   MI_AD(T_Q8_0, T_Q4_0);
 #undef MI_AD
+#undef MI_AD1
     }
     if (v_trans && kt == T_Q8_0) {
         if (head_dim == 128) hipLaunchKernelGGL((k_attn_decode<128, true, T_Q8_0>), grid, dim3(256), lds, stream, a);
@@ -478,8 +605,14 @@ void attn_decode(const void * q, size_t q_nb1, size_t q_nb2, const void * k, siz
     }
     if (a.nsplit > 1) {
         const dim3 mg((unsigned) n_head, (unsigned) T);
-        if (head_dim == 128) hipLaunchKernelGGL((k_attn_merge<128>), mg, dim3(128), 0, stream, a);
-        else                 hipLaunchKernelGGL((k_attn_merge<64>),  mg, dim3(64),  0, stream, a);
+        switch (hsv) {
+            case 128: hipLaunchKernelGGL((k_attn_merge<128>), mg, dim3(128), 0, stream, a); break;
+            case 64:  hipLaunchKernelGGL((k_attn_merge<64>),  mg, dim3(64),  0, stream, a); break;
+            case 80:  hipLaunchKernelGGL((k_attn_merge<80>),  mg, dim3(80),  0, stream, a); break;
+            case 96:  hipLaunchKernelGGL((k_attn_merge<96>),  mg, dim3(96),  0, stream, a); break;
+            case 192: hipLaunchKernelGGL((k_attn_merge<192>), mg, dim3(192), 0, stream, a); break;
+            default:  hipLaunchKernelGGL((k_attn_merge<256>), mg, dim3(256), 0, stream, a); break;
+        }
     }
 }
 

@@ -54,8 +54,14 @@ MODELS = {
     "tiny-oai": dict(n_embd=128, n_ff=128, n_layer=2, n_head=8, n_head_kv=2, n_embd_head=64, n_vocab=512,
                      rope_freq_base=10000.0, n_ctx_orig=256, is_70b=0, n_expert=8, n_expert_used=4, arch=1, rope_type=2,
                      n_swa=16, swa_pattern=2, n_ubatch=8),
-    # head size 128 with GQA 4:1 at test size (the fused attention kernels are instantiated for 64 and 128)
+    # head size 128 with GQA 4:1 at test size (the fused attention kernels of the graph without flash attention are instantiated for 64 and 128)
     "tiny-hd128": dict(n_embd=512, n_ff=512, n_layer=2, n_head=4, n_head_kv=1, n_embd_head=128, n_vocab=512,
+                       rope_freq_base=10000.0, n_ctx_orig=256, is_70b=0),
+    # head sizes 96 (8 heads over 2 KV heads) and 256 (2 heads over 1): FLASH_ATTN_EXT's other head sizes at test size (n_embd and n_ff stay multiples of
+    # 256 for the K-quant mat-vecs)
+    "tiny-hd96": dict(n_embd=768, n_ff=768, n_layer=2, n_head=8, n_head_kv=2, n_embd_head=96, n_vocab=512,
+                      rope_freq_base=10000.0, n_ctx_orig=256, is_70b=0),
+    "tiny-hd256": dict(n_embd=512, n_ff=512, n_layer=2, n_head=2, n_head_kv=1, n_embd_head=256, n_vocab=512,
                        rope_freq_base=10000.0, n_ctx_orig=256, is_70b=0),
     # ONE Llama-3-8B-shaped layer with a small vocabulary: the prefill fusions (grouped QKV with ROPE and KV store in its combine pass, 16-wave
     # tiles, gate/up/SwiGLU, split-k combine + norm) only engage at these sizes with >= 256 tokens
