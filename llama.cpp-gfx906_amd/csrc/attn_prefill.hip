@@ -299,68 +299,61 @@ __global__ void __launch_bounds__(64*NW) k_attn_prefill(const attn_pf_args p, in
     }
 }
 
+// ---- the prefill launch, planned once (kernels.h: attn_call, attn_prefill_plan) ----
+attn_prefill_plan attn_plan_prefill(const attn_call & c) {
+    static const bool ks4_on = env_on("GGML_MI355X_ATTN_PF_KS4");
+    attn_prefill_plan pl = {};
+    pl.ok = c.q_type == T_F32 && c.k_type == T_F16 && c.v_type == T_F16 && c.n_kv % 32 == 0 && c.n_kv > 0 && c.n_head_kv > 0 && c.n_head % c.n_head_kv == 0 &&
+            (c.v_trans ? attn_fa_head_sizes(c.hsk, c.hsv, T_F16, T_F16) : c.hsv == c.hsk && (c.hsk == 64 || c.hsk == 128));
+    if (!pl.ok) return pl;
+    pl.nw = c.hsk > 128 ? 4 : APF_NW;                                       // waves per workgroup (the kernel's NW)
+    const int64_t R = c.n_head/c.n_head_kv, T = c.T;
+    pl.hpw = R % 8 == 0 && pl.nw >= 8 ? 8 : R % 4 == 0 ? 4 : R % 2 == 0 ? 2 : 1;          // heads of one kv head per workgroup
+    // few workgroups (short prompts): the waves of a (head, query tile) split the cell blocks of an iteration two or four ways, shortening the loop that is the critical path
+    const int64_t wgs1 = ((T + 32*(pl.nw/pl.hpw) - 1)/(32*(pl.nw/pl.hpw)))*(c.n_head/pl.hpw);
+    pl.ks = (pl.hpw*2 <= pl.nw && pl.hpw <= 4 && wgs1 < 160 && c.n_kv >= 128) ? 2 : 1;
+    if (ks4_on && pl.ks == 2 && R % 2 == 0 && c.n_kv >= 256 && c.hsk == 128 && c.v_trans) {
+        // ... four ways with two heads per workgroup when even the pairs leave half the chip idle (pp512 of a 32-head model: 128 workgroups -> 256)
+        const int64_t wgs2 = ((T + 32*(APF_NW/(pl.hpw*2)) - 1)/(32*(APF_NW/(pl.hpw*2))))*(c.n_head/pl.hpw);
+        if (wgs2 < 200) { pl.hpw = 2; pl.ks = 4; }
+    }
+    const int qpw = pl.nw/(pl.hpw*pl.ks);                                            // query tiles per workgroup
+    pl.grid = dim3((unsigned)((T + 32*qpw - 1)/(32*qpw)), (unsigned)(c.n_head/pl.hpw));
+    return pl;
+}
+
 // One instantiation's launch. LDS: the staging buffers 2*KS*(32*(HDK*2 + 16) + HDVP*72), HDVP = HDV rounded up to 32 — 141 KB at 256 with KS = 2, of a CU's
 // 160 KB; the wave pairs' merge at the end reuses them and is the larger of the two at 80 only: NW/2 receivers x (16*NDT + 2) floats x 64 lanes.
-// KS = 4 exists for the transposed-V form at 128 only (the host never asks for another).
-struct apf_launch_args { const attn_pf_args & a; int hpw; dim3 grid; hipStream_t stream; };
+// KS = 4 exists for the transposed-V form at 128 only (the plan never asks for another).
 template <int HD, bool VT, int MK, int KS, int HV, int NW>
-static void apf_launch(const apf_launch_args & l) {
+static void apf_launch(const attn_pf_args & a, const attn_prefill_plan & pl, hipStream_t stream) {
     if constexpr (KS == 4 && !(HD == 128 && VT)) { fprintf(stderr, "attn_prefill: no four-way form at head size %d\n", HD); abort(); }
     else {
         constexpr size_t ndt = (HV + 31)/32, st = (size_t) 2*KS*(32*(HD*2 + APF_KLD) + ndt*32*(64 + 8)), mg = KS > 1 ? (size_t)(NW/2)*(16*ndt + 2)*256 : 0;
         constexpr size_t lds = st > mg ? st : mg;
         static_assert(lds <= (size_t) 160*1024, "a workgroup's LDS");
         MI_LDS_LIMIT_OR_DIE(lds, k_attn_prefill<HD, VT, MK, KS, HV, NW>);
-        hipLaunchKernelGGL((k_attn_prefill<HD, VT, MK, KS, HV, NW>), l.grid, dim3(64*NW), lds, l.stream, l.a, l.hpw);
+        hipLaunchKernelGGL((k_attn_prefill<HD, VT, MK, KS, HV, NW>), pl.grid, dim3(64*NW), lds, stream, a, pl.hpw);
     }
 }
 
-bool attn_prefill_supported(int64_t head_dim, int64_t n_kv) { return (head_dim == 128 || head_dim == 64) && n_kv % 32 == 0 && n_kv > 0; }
-
-void attn_prefill(const void * q, size_t q_nb1, size_t q_nb2, const void * k, size_t k_nb1, size_t k_nb2, const void * v, size_t v_nb1, size_t v_nb2,
-                  const void * mask, size_t m_nb1, bool mask_f16, const float * sinks, float * dst, size_t dst_nb1,
-                  int64_t head_dim, int64_t n_kv, int64_t n_head, int64_t n_head_kv, int64_t T, float scale, hipStream_t stream, bool v_trans, uint16_t * y16, const attn_extra * ex) {
-    const int64_t hsv = ex && ex->hsv ? ex->hsv : head_dim;
-    if (v_trans ? !attn_fa_head_sizes(head_dim, hsv, T_F16, T_F16) : !(hsv == head_dim && (head_dim == 64 || head_dim == 128))) {
-        fprintf(stderr, "attn_prefill: head sizes (%lld, %lld) have no kernel\n", (long long) head_dim, (long long) hsv); abort();
-    }
-    attn_pf_args a = { (const char *) q, q_nb1, q_nb2, (const char *) k, k_nb1, k_nb2, (const char *) v, v_nb1, v_nb2,
-                       (const char *) mask, m_nb1, mask_f16 ? 1 : 0, sinks, dst, dst_nb1, y16, (int)((hsv*n_head + 63) & ~(int64_t) 63), (int) n_kv, (int) n_head, (int) n_head_kv, (int) T, scale,
-                       0.0f, 0.0f, 1.0f, 1.0f, 1 };
-    if (ex) {
-        attn_alibi(ex->max_bias, n_head, a.m0, a.m1, a.n_head_log2);
-        a.softcap = ex->softcap; a.max_bias = ex->max_bias;
-        if (ex->softcap != 0.0f) a.scale = scale/ex->softcap;
-    }
-    const int nw = head_dim > 128 ? 4 : APF_NW;                             // waves per workgroup (the kernel's NW)
-    const int64_t R = n_head/n_head_kv;
-    int hpw = R % 8 == 0 && nw >= 8 ? 8 : R % 4 == 0 ? 4 : R % 2 == 0 ? 2 : 1;          // heads of one kv head per workgroup
-    // few workgroups (short prompts): the waves of a (head, query tile) split the cell blocks of an iteration two or four ways, shortening the loop that is the critical path
-    const int64_t wgs1 = ((T + 32*(nw/hpw) - 1)/(32*(nw/hpw)))*(n_head/hpw);
-    int ksp = (hpw*2 <= nw && hpw <= 4 && wgs1 < 160 && n_kv >= 128) ? 2 : 1;
-    static const bool ks4_on = env_on("GGML_MI355X_ATTN_PF_KS4");
-    if (ks4_on && ksp == 2 && R % 2 == 0 && n_kv >= 256 && head_dim == 128 && v_trans) {
-        // ... four ways with two heads per workgroup when even the pairs leave half the chip idle (pp512 of a 32-head model: 128 workgroups -> 256)
-        const int64_t wgs2 = ((T + 32*(APF_NW/(hpw*2)) - 1)/(32*(APF_NW/(hpw*2))))*(n_head/hpw);
-        if (wgs2 < 200) { hpw = 2; ksp = 4; }
-    }
-    const int qpw = nw/(hpw*ksp);                                                    // query tiles per workgroup
-    const dim3 grid((unsigned)((T + 32*qpw - 1)/(32*qpw)), (unsigned)(n_head/hpw));
-    const int mk = !mask ? 0 : (mask_f16 ? 2 : 1);
-    const apf_launch_args la = { a, hpw, grid, stream };
-#define MI_APF1(HD_, VT_, MK_, HV_, NW_) do { if (ksp == 4) apf_launch<HD_, VT_, MK_, 4, HV_, NW_>(la); else if (ksp == 2) apf_launch<HD_, VT_, MK_, 2, HV_, NW_>(la); else apf_launch<HD_, VT_, MK_, 1, HV_, NW_>(la); } while (0)
-#define MI_APF(HD_, VT_, HV_, NW_) do { if (mk == 0) MI_APF1(HD_, VT_, 0, HV_, NW_); else if (mk == 1) MI_APF1(HD_, VT_, 1, HV_, NW_); else MI_APF1(HD_, VT_, 2, HV_, NW_); } while (0)
-    // the (hsk, hsv) pairs of attn_fa_head_sizes, one set of instantiations each
-    if (!v_trans) { if (head_dim == 128) MI_APF(128, false, 128, APF_NW); else MI_APF(64, false, 64, APF_NW); }
-    else if (head_dim == 128) MI_APF(128, true, 128, APF_NW);
-    else if (head_dim == 64)  MI_APF(64, true, 64, APF_NW);
-    else if (head_dim == 80)  MI_APF(80, true, 80, APF_NW);
-    else if (head_dim == 96)  MI_APF(96, true, 96, APF_NW);
-    else if (head_dim == 256) MI_APF(256, true, 256, 4);
-    else if (hsv == 192)      MI_APF(192, true, 192, 4);
-    else                      MI_APF(192, true, 128, 4);
-#undef MI_APF
-#undef MI_APF1
+void attn_prefill(const attn_call & c) {
+    const attn_prefill_plan pl = attn_plan_prefill(c);
+    if (!pl.ok) { fprintf(stderr, "attn_prefill: no kernel for head sizes (%lld, %lld), KV types (%d, %d), %lld cells\n", (long long) c.hsk, (long long) c.hsv, c.k_type, c.v_type, (long long) c.n_kv); abort(); }
+    attn_pf_args a = {};
+    a.q = (const char *) c.q; a.q_nb1 = c.q_nb1; a.q_nb2 = c.q_nb2;
+    a.k = (const char *) c.k; a.k_nb1 = c.k_nb1; a.k_nb2 = c.k_nb2;
+    a.v = (const char *) c.v; a.v_nb1 = c.v_nb1; a.v_nb2 = c.v_nb2;
+    if (c.mask_type != T_NONE) { a.mask = (const char *) c.mask; a.m_nb1 = c.m_nb1; a.mask_f16 = c.mask_type == T_F16; }
+    a.sinks = c.sinks; a.dst = c.dst; a.dst_nb1 = c.dst_nb1; a.y16 = c.y16; a.kp16 = (int)((c.hsv*c.n_head + 63) & ~(int64_t) 63);
+    a.n_kv = (int) c.n_kv; a.n_head = (int) c.n_head; a.n_head_kv = (int) c.n_head_kv; a.T = (int) c.T;
+    attn_set_softmax(a, c);
+    // the (hsk, hsv) pairs of attn_fa_head_sizes x the mask's kind (0 = none, 1 = f32, 2 = f16) x the plan's ks, one instantiation each
+    attn_dispatch_sizes(c.hsk, c.hsv, [&](auto hk, auto hv) { attn_dispatch_int<0, 1, 2>(c.mask_type == T_NONE ? 0 : c.mask_type == T_F16 ? 2 : 1, [&](auto mk) { attn_dispatch_int<1, 2, 4>(pl.ks, [&](auto ks) {
+        constexpr int HK = decltype(hk)::value, HV = decltype(hv)::value, MK = decltype(mk)::value, KS = decltype(ks)::value, NW = HK > 128 ? 4 : APF_NW;
+        if (c.v_trans) apf_launch<HK, true, MK, KS, HV, NW>(a, pl, c.stream);
+        else if constexpr (HK == HV && (HK == 64 || HK == 128)) apf_launch<HK, false, MK, KS, HV, NW>(a, pl, c.stream);
+    }); }); });
 }
 
 // ---- the cache as the kernels above want it: f16, cells as rows or transposed (kv_types.h has the element types) ----
@@ -402,11 +395,11 @@ void kv_to_f16(int type, const void * src, size_t nb1, size_t nb2, int64_t hd, i
     if (hd % 8 || hd < 8 || hd > 256 || ((type == T_Q8_0 || type == T_Q4_0) && hd % 32) || n_kv % 8 || n_kv < 8) { fprintf(stderr, "kv_to_f16: unsupported shape (hd %lld, n_kv %lld)\n", (long long) hd, (long long) n_kv); abort(); }
     const kvc_args a = { (const char *) src, nb1, nb2, (int) hd, (int) n_kv, (int) n_head_kv, dst };
     const long long tot = (long long) n_head_kv*n_kv*(hd/8);
-#define MI_KVC(TY_) do { if (transpose) hipLaunchKernelGGL((k_kv_trans_f16<TY_>), dim3((unsigned)((n_kv + 63)/64), (unsigned) n_head_kv, (unsigned)((hd + 127)/128)), dim3(256), 0, stream, a); \
-                         else hipLaunchKernelGGL((k_kv_rows_f16<TY_>), dim3((unsigned)((tot + 255)/256)), dim3(256), 0, stream, a); } while (0)
-    if (type == T_F16) MI_KVC(T_F16); else if (type == T_BF16) MI_KVC(T_BF16); else if (type == T_Q8_0) MI_KVC(T_Q8_0); else if (type == T_Q4_0) MI_KVC(T_Q4_0);
-    else { fprintf(stderr, "kv_to_f16: cache type %d is not supported\n", type); abort(); }
-#undef MI_KVC
+    if (!attn_dispatch_int<T_F16, T_BF16, T_Q8_0, T_Q4_0>(type, [&](auto ty) {
+            constexpr int TY = decltype(ty)::value;
+            if (transpose) hipLaunchKernelGGL((k_kv_trans_f16<TY>), dim3((unsigned)((n_kv + 63)/64), (unsigned) n_head_kv, (unsigned)((hd + 127)/128)), dim3(256), 0, stream, a);
+            else           hipLaunchKernelGGL((k_kv_rows_f16<TY>), dim3((unsigned)((tot + 255)/256)), dim3(256), 0, stream, a);
+        })) { fprintf(stderr, "kv_to_f16: cache type %d is not supported\n", type); abort(); }
 }
 
 } // namespace mi355x

@@ -496,7 +496,7 @@ static bool mi_supports_op(const struct ggml_tensor * op) {
             if (k->nb[1] % (k->type == GGML_TYPE_F16 || k->type == GGML_TYPE_BF16 ? 16 : 2) || k->nb[2] % (k->type == GGML_TYPE_F16 || k->type == GGML_TYPE_BF16 ? 16 : 2)) return false;
             if (v->nb[1] % (v->type == GGML_TYPE_F16 || v->type == GGML_TYPE_BF16 ? 16 : 2) || v->nb[2] % (v->type == GGML_TYPE_F16 || v->type == GGML_TYPE_BF16 ? 16 : 2)) return false;
             // the head sizes, and the shapes: a few tokens' score row in LDS or their cell ranges through the fixed partial-result buffer; many tokens: 32-cell blocks
-            return attn_fa_supported(k->ne[0], v->ne[0], (int) k->type, (int) v->type, k->ne[1], s0->ne[2], s0->ne[1], ATTN_PART_BYTES);
+            return fa_kv16_plan(op, nullptr, nullptr, ATTN_PART_BYTES).ok;
         }
         case GGML_OP_RMS_NORM:
             return s0->type == GGML_TYPE_F32 && op->type == GGML_TYPE_F32 && s0->nb[0] == sizeof(float);

@@ -229,7 +229,7 @@ static enum ggml_status prepare_buffers(mi_backend_ctx * c, const struct ggml_cg
     }
     {
         size_t kv_need = 0;
-        for (int i = 0; i < g->n_nodes; i++) if (g->nodes[i]->op == GGML_OP_FLASH_ATTN_EXT) { size_t kb, vb; fa_kv16_plan(g->nodes[i], kb, vb); kv_need = std::max(kv_need, kb + vb); }
+        for (int i = 0; i < g->n_nodes; i++) if (g->nodes[i]->op == GGML_OP_FLASH_ATTN_EXT) { const fa_operands p = fa_kv16_plan(g->nodes[i], nullptr, nullptr, 0); kv_need = std::max(kv_need, p.k_bytes + p.v_bytes); }
         if (kv_need > c->kv16_size) {
             MI_CHECK_G(hipStreamSynchronize(c->stream));
             if (c->kv16) MI_CHECK_G(hipFree(c->kv16));

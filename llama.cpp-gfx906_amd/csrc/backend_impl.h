@@ -235,7 +235,8 @@ void prof_end(mi_backend_ctx * c);
 // backend_nodes.cpp
 int  compute_node(mi_backend_ctx * c, struct ggml_cgraph * g, int i);     // returns the number of graph nodes consumed (>= 1)
 void pass_end(mi_backend_ctx * c);                                         // the last node of a pass has run: the pending combine runs, aq ends
-void fa_kv16_plan(const struct ggml_tensor * n, size_t & k_bytes, size_t & v_bytes);
+struct fa_operands { bool ok; size_t k_bytes, v_bytes; attn_call call; };
+fa_operands fa_kv16_plan(const struct ggml_tensor * n, void * kv16, float * part, size_t part_bytes);
 // backend_graph.cpp
 enum ggml_status be_graph_compute(ggml_backend_t backend, struct ggml_cgraph * g);
 void drop_graphs(mi_backend_ctx * c);

@@ -40,14 +40,35 @@ void pass_end(mi_backend_ctx * c) {
     c->pass.drop_act();
 }
 
-// FLASH_ATTN_EXT: the dense f16 copies its kernels need — the V cache transposed for the matrix-core prefill kernel (always: rows over cells are what it
-// stages with coalesced loads), K when it is not f16; for a few tokens only what the decode kernel does not read directly (attn_decode_kv_types_fused)
-void fa_kv16_plan(const struct ggml_tensor * n, size_t & k_bytes, size_t & v_bytes) {
+// FLASH_ATTN_EXT as its kernels get it: the dense f16 copies they need (kv_to_f16 into kv16, K first and V behind it) — the V cache transposed for the matrix-core
+// prefill kernel (always: rows over cells are what it stages with coalesced loads), K when it is not f16; for a few tokens only what the decode kernel does not read
+// directly (attn_decode_kv_types_fused) — and the launch's operands after them. ok: the cache's types have kernels at these head sizes and the launch has a plan
+// with the partial buffer on offer. kv16 may be NULL (supports_op, sizing kv16: nothing is launched from the result).
+fa_operands fa_kv16_plan(const struct ggml_tensor * n, void * kv16, float * part, size_t part_bytes) {
     const struct ggml_tensor * q = n->src[0]; const struct ggml_tensor * k = n->src[1]; const struct ggml_tensor * v = n->src[2];
-    const size_t k_dense = (((size_t) k->ne[0]*k->ne[1]*k->ne[2]*2) + 255) & ~(size_t) 255, v_dense = (((size_t) v->ne[0]*v->ne[1]*v->ne[2]*2) + 255) & ~(size_t) 255;
-    if (q->ne[1] > 8) { k_bytes = k->type != GGML_TYPE_F16 ? k_dense : 0; v_bytes = v_dense; }
-    else if (attn_decode_kv_types_fused((int) k->type, (int) v->type)) { k_bytes = v_bytes = 0; }
-    else { k_bytes = k->type != GGML_TYPE_F16 ? k_dense : 0; v_bytes = v->type != GGML_TYPE_F16 ? v_dense : 0; }
+    const struct ggml_tensor * mask = n->src[3]; const struct ggml_tensor * sinks = n->src[4];
+    fa_operands p = {};
+    attn_call & a = p.call;
+    a.hsk = k->ne[0]; a.hsv = v->ne[0]; a.n_kv = k->ne[1]; a.n_head = q->ne[2]; a.n_head_kv = k->ne[2]; a.T = q->ne[1];
+    a.q = q->data; a.q_nb1 = q->nb[1]; a.q_nb2 = q->nb[2]; a.q_type = (int) q->type;
+    a.k = k->data; a.k_nb1 = k->nb[1]; a.k_nb2 = k->nb[2]; a.k_type = (int) k->type;
+    a.v = v->data; a.v_nb1 = v->nb[1]; a.v_nb2 = v->nb[2]; a.v_type = (int) v->type;
+    if (mask) { a.mask = mask->data; a.m_nb1 = mask->nb[1]; a.mask_type = (int) mask->type; }
+    a.sinks = sinks ? (const float *) sinks->data : nullptr; a.dst = (float *) n->data; a.dst_nb1 = n->nb[2];
+    a.scale = op_f32(n, 0); a.max_bias = op_f32(n, 1); a.softcap = op_f32(n, 2);
+    a.part = part; a.part_bytes = part_bytes;
+    const bool prefill = a.T > 8, direct = !prefill && attn_decode_kv_types_fused(a.k_type, a.v_type);
+    if (!direct && k->type != GGML_TYPE_F16) {
+        p.k_bytes = (((size_t) a.hsk*a.n_kv*a.n_head_kv*2) + 255) & ~(size_t) 255;
+        a.k = kv16; a.k_nb1 = (size_t) a.hsk*2; a.k_nb2 = (size_t) a.n_kv*a.hsk*2; a.k_type = T_F16;
+    }
+    if (!direct && (prefill || v->type != GGML_TYPE_F16)) {
+        p.v_bytes = (((size_t) a.hsv*a.n_kv*a.n_head_kv*2) + 255) & ~(size_t) 255;
+        a.v = kv16 ? (char *) kv16 + p.k_bytes : nullptr; a.v_type = T_F16; a.v_trans = prefill;
+        a.v_nb1 = (size_t)(prefill ? a.n_kv : a.hsv)*2; a.v_nb2 = (size_t) a.hsv*a.n_kv*2;
+    }
+    p.ok = attn_fa_head_sizes(a.hsk, a.hsv, (int) k->type, (int) v->type) && attn_supported(a);
+    return p;
 }
 
 // quantize (or reuse) the activations of a quantized mat-mul: rows r -> x + (r % n_inner)*s_inner + (r / n_inner)*s_outer
@@ -227,34 +248,24 @@ static void op_mul_mat_id(mi_backend_ctx * c, struct ggml_tensor * dst) {
 
 static void op_flash_attn_ext(mi_backend_ctx * c, struct ggml_tensor * node) {
     const struct ggml_tensor * q = node->src[0]; const struct ggml_tensor * k = node->src[1]; const struct ggml_tensor * v = node->src[2];
-    const struct ggml_tensor * mask = node->src[3]; const struct ggml_tensor * sinks = node->src[4];
+    const struct ggml_tensor * mask = node->src[3];
     const int64_t hd = k->ne[0], hsv = v->ne[0], n_kv = k->ne[1], T = q->ne[1];      // hd: K's head size
     // what supports_op cannot see (data alignment of the views handed in) fails the graph instead of the process
     MI_REQUIRE_G(node->nb[1] == (size_t) hsv*4 && ((uintptr_t) q->data % 16) == 0);
     MI_REQUIRE_G(((uintptr_t) k->data % (k->type == GGML_TYPE_F16 || k->type == GGML_TYPE_BF16 ? 16 : 2)) == 0 && ((uintptr_t) v->data % (v->type == GGML_TYPE_F16 || v->type == GGML_TYPE_BF16 ? 16 : 2)) == 0);
     MI_REQUIRE_G(!mask || (mask->ne[0] == n_kv && mask->ne[1] >= T && ((uintptr_t) mask->data % 16) == 0 && mask->nb[1] % 16 == 0));
-    MI_REQUIRE_G(attn_fa_supported(hd, hsv, (int) k->type, (int) v->type, n_kv, q->ne[2], T, c->attn_part ? c->attn_part_bytes : 0));
-    attn_extra ex = { op_f32(node, 2), op_f32(node, 1), (int) k->type, (int) v->type, (int) hsv };
-    const void * kd = k->data; const void * vd = v->data;
-    size_t k_nb1 = k->nb[1], k_nb2 = k->nb[2], v_nb1 = v->nb[1], v_nb2 = v->nb[2];
-    size_t kb, vb; fa_kv16_plan(node, kb, vb);
-    MI_REQUIRE_G(kb + vb <= c->kv16_size);
-    bool v_trans = false;
-    if (kb) {
-        kv_to_f16((int) k->type, k->data, k->nb[1], k->nb[2], hd, n_kv, k->ne[2], (uint16_t *) c->kv16, false, c->stream);
-        kd = c->kv16; k_nb1 = (size_t) hd*2; k_nb2 = (size_t) n_kv*hd*2; ex.k_type = T_F16; c->cnt.kernels_launched++;
+    fa_operands p = fa_kv16_plan(node, c->kv16, c->attn_part, c->attn_part_bytes);
+    MI_REQUIRE_G(p.ok && p.k_bytes + p.v_bytes <= c->kv16_size);
+    p.call.stream = c->stream;
+    if (p.k_bytes) {
+        kv_to_f16((int) k->type, k->data, k->nb[1], k->nb[2], hd, n_kv, k->ne[2], (uint16_t *) c->kv16, /* transpose */ false, c->stream);
+        c->cnt.kernels_launched++;
     }
-    if (vb) {
-        v_trans = T > 8;
-        kv_to_f16((int) v->type, v->data, v->nb[1], v->nb[2], hsv, n_kv, v->ne[2], (uint16_t *) ((char *) c->kv16 + kb), v_trans, c->stream);
-        vd = (char *) c->kv16 + kb; ex.v_type = T_F16; c->cnt.kernels_launched++;
-        if (v_trans) { v_nb1 = (size_t) n_kv*2; v_nb2 = (size_t) hsv*n_kv*2; } else { v_nb1 = (size_t) hsv*2; v_nb2 = (size_t) n_kv*hsv*2; }
+    if (p.v_bytes) {
+        kv_to_f16((int) v->type, v->data, v->nb[1], v->nb[2], hsv, n_kv, v->ne[2], (uint16_t *) ((char *) c->kv16 + p.k_bytes), p.call.v_trans, c->stream);
+        c->cnt.kernels_launched++;
     }
-    if (T <= 8) attn_decode(q->data, q->nb[1], q->nb[2], kd, k_nb1, k_nb2, vd, v_nb1, v_nb2, mask ? mask->data : nullptr, mask ? mask->nb[1] : 0, true,
-                            sinks ? (const float *) sinks->data : nullptr, (float *) node->data, node->nb[2], hd, n_kv, q->ne[2], k->ne[2], T, op_f32(node, 0), c->stream, false,
-                            c->attn_part, c->attn_part_bytes, false, &ex);
-    else        attn_prefill(q->data, q->nb[1], q->nb[2], kd, k_nb1, k_nb2, vd, v_nb1, v_nb2, mask ? mask->data : nullptr, mask ? mask->nb[1] : 0, true,
-                             sinks ? (const float *) sinks->data : nullptr, (float *) node->data, node->nb[2], hd, n_kv, q->ne[2], k->ne[2], T, op_f32(node, 0), c->stream, v_trans, nullptr, &ex);
+    if (T <= 8) attn_decode(p.call); else attn_prefill(p.call);
     c->cnt.kernels_launched++;
 }
 
@@ -623,8 +634,7 @@ static int try_fused_attn(mi_backend_ctx * c, struct ggml_cgraph * g, int i) {
     if ((k->type != GGML_TYPE_F16 && !kq8) || q->type != GGML_TYPE_F32 || k->ne[3] != 1 || q->ne[3] != 1) return 0;
     const int64_t hd = k->ne[0], n_kv = k->ne[1], n_head_kv = k->ne[2], T = q->ne[1], n_head = q->ne[2];
     const bool prefill = T > 8;      // many tokens: the matrix-core kernel with online softmax (attn_prefill.hip)
-    if (kq8 && (prefill || k->nb[0] != 34 || k->nb[2] != (size_t) hd/32*34 || k->nb[1] % 2 || (uintptr_t) k->data % 2)) return 0;
-    if (n_head % n_head_kv != 0 || !(prefill ? attn_prefill_supported(hd, n_kv) : (attn_decode_supported(hd, n_kv) || (c->attn_part && attn_decode_supported_split(hd, n_kv) && attn_decode_part_bytes(hd, n_kv, n_head, T) <= c->attn_part_bytes)))) return 0;
+    if (kq8 && (k->nb[0] != 34 || k->nb[2] != (size_t) hd/32*34 || k->nb[1] % 2 || (uintptr_t) k->data % 2)) return 0;
     if ((!kq8 && (k->nb[0] != 2 || k->nb[1] % 16 || k->nb[2] % 16 || (uintptr_t) k->data % 16)) || q->nb[0] != 4 || q->nb[1] % 16 || q->nb[2] % 16 || (uintptr_t) q->data % 16) return 0;
     const int j1 = next_real(g, i); if (j1 < 0) return 0;
     struct ggml_tensor * sm = g->nodes[j1];
@@ -644,35 +654,26 @@ static int try_fused_attn(mi_backend_ctx * c, struct ggml_cgraph * g, int i) {
     if (pm->op != GGML_OP_PERMUTE || pm->src[0] != kqv || !is_internal(c, pm)) return 0;
     if (pm->ne[0] != hd || pm->ne[1] != n_head || pm->ne[2] != T || pm->ne[3] != 1) return 0;
     if (ct->type != GGML_TYPE_F32 || !ggml_is_contiguous(ct) || ggml_nelements(ct) != hd*n_head*T) return 0;
+    attn_call a = {};
+    a.hsk = a.hsv = hd; a.n_kv = n_kv; a.n_head = n_head; a.n_head_kv = n_head_kv; a.T = T;
+    a.q = q->data; a.q_nb1 = q->nb[1]; a.q_nb2 = q->nb[2]; a.q_type = (int) q->type;
+    a.k = k->data; a.k_nb1 = k->nb[1]; a.k_nb2 = k->nb[2]; a.k_type = (int) k->type;
+    a.v = v->data; a.v_nb1 = v->nb[1]; a.v_nb2 = v->nb[2]; a.v_type = (int) v->type; a.v_trans = true;
+    if (mask) { a.mask = mask->data; a.m_nb1 = mask->nb[1]; a.mask_type = (int) mask->type; }
+    a.sinks = sm->src[2] ? (const float *) sm->src[2]->data : nullptr; a.dst = (float *) ct->data; a.dst_nb1 = (size_t) hd*n_head*4;
+    a.scale = op_f32(sm, 0); a.part = c->attn_part; a.part_bytes = c->attn_part_bytes; a.stream = c->stream;
+    // the chain is taken at head sizes 64 / 128 only, as it always was (the prefill kernel's transposed-V form has FLASH_ATTN_EXT's other sizes too); prompts over a Q8_0 K cache keep the generic ops
+    if ((hd != 64 && hd != 128) || !attn_supported(a)) return 0;
     if (prefill) {
         if (mask && (mask->ne[1] < T || ((uintptr_t) mask->data % 16) || mask->nb[1] % 16)) return 0;
         if (v->nb[1] % 8 || v->nb[2] % 8 || ((uintptr_t) v->data % 8)) return 0;
         // wo reads the result next: hand it the bf16 copy directly (nothing reads the scratch's offset 0 during this kernel)
         const struct ggml_tensor * wo = prefill_mm_consumer(c, g, j3, ct);
-        const bool y16 = wo && mul_mat_q_scratch_bytes(hd*n_head, T, wo->src[0]->ne[1]) <= c->scratch_size;
-        attn_prefill(q->data, q->nb[1], q->nb[2], k->data, k->nb[1], k->nb[2], v->data, v->nb[1], v->nb[2],
-                     mask ? mask->data : nullptr, mask ? mask->nb[1] : 0, mask && mask->type == GGML_TYPE_F16,
-                     sm->src[2] ? (const float *) sm->src[2]->data : nullptr, y16 ? nullptr : (float *) ct->data, (size_t) hd*n_head*4,
-                     hd, n_kv, n_head, n_head_kv, T, op_f32(sm, 0), c->stream, true, y16 ? (uint16_t *) c->scratch : nullptr);
-        if (y16) c->pass.produced_bf16(i, j3, ct->data, hd*n_head, T, ct->nb[1], 0);
-        c->cnt.kernels_launched++;
-        return j3 - i + 1;
-    }
-    if (kq8) {
-        const bool use_part = c->attn_part && attn_decode_part_bytes(hd, n_kv, n_head, T) <= c->attn_part_bytes;
-        attn_decode(q->data, q->nb[1], q->nb[2], k->data, k->nb[1], k->nb[2], v->data, v->nb[1], v->nb[2], mask ? mask->data : nullptr, mask ? mask->nb[1] : 0,
-                    mask && mask->type == GGML_TYPE_F16, sm->src[2] ? (const float *) sm->src[2]->data : nullptr, (float *) ct->data, (size_t) hd*n_head*4,
-                    hd, n_kv, n_head, n_head_kv, T, op_f32(sm, 0), c->stream, true, use_part ? c->attn_part : nullptr, use_part ? c->attn_part_bytes : 0, true);
-        c->cnt.kernels_launched++;
-        return j3 - i + 1;
-    }
-    {
-        const bool use_part = c->attn_part && attn_decode_part_bytes(hd, n_kv, n_head, T) <= c->attn_part_bytes;
-        attn_decode(q->data, q->nb[1], q->nb[2], k->data, k->nb[1], k->nb[2], v->data, v->nb[1], v->nb[2], mask ? mask->data : nullptr, mask ? mask->nb[1] : 0,
-                    mask && mask->type == GGML_TYPE_F16, sm->src[2] ? (const float *) sm->src[2]->data : nullptr, (float *) ct->data, (size_t) hd*n_head*4,
-                    hd, n_kv, n_head, n_head_kv, T, op_f32(sm, 0), c->stream, true, use_part ? c->attn_part : nullptr, use_part ? c->attn_part_bytes : 0);
-        c->cnt.kernels_launched++;
-    }
+        if (wo && mul_mat_q_scratch_bytes(hd*n_head, T, wo->src[0]->ne[1]) <= c->scratch_size) { a.y16 = (uint16_t *) c->scratch; a.dst = nullptr; }
+        attn_prefill(a);
+        if (a.y16) c->pass.produced_bf16(i, j3, ct->data, hd*n_head, T, ct->nb[1], 0);
+    } else attn_decode(a);
+    c->cnt.kernels_launched++;
     return j3 - i + 1;
 }
 

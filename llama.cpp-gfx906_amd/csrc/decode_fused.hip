@@ -496,124 +496,72 @@ __global__ void __launch_bounds__(HD) k_attn_merge(const attn_args p) {
     *(float *) ((char *) p.dst + (size_t) t*p.dst_nb1 + (size_t)(h*HD + d)*4) = acc/den;
 }
 
-// without a partial buffer the whole row of scores must fit the workgroup's LDS
-static bool attn_one_wg_shape(int64_t n_kv) { return n_kv % 8 == 0 && n_kv*4 <= 48*1024; }
-bool attn_decode_supported(int64_t head_dim, int64_t n_kv) { return (head_dim == 128 || head_dim == 64) && attn_one_wg_shape(n_kv); }
-// measured (tg1024 / --fa 1 tg128): the transposed-V kernel gains from 384-512 cells on, the row-V (flash attention) one already at 256
-static int64_t attn_split_min(bool v_trans = true) {
+// ---- the decode launch, planned once (kernels.h: attn_call, attn_decode_plan) ----
+// where the cells start to be split. Measured (tg1024 / --fa 1 tg128): the transposed-V kernel gains from 384-512 cells on, the row-V (flash attention) one already at 256
+static int64_t attn_split_min(bool v_trans) {
     static const int64_t v = env_int("GGML_MI355X_ATTN_SPLIT_MIN", 0);
     return v ? (v < 256 ? 256 : v) : (v_trans ? 384 : 256);
 }
-static bool attn_split_shape(int64_t n_kv) { return n_kv >= attn_split_min(true) && n_kv % 32 == 0; }
-bool attn_decode_supported_split(int64_t head_dim, int64_t n_kv) { return (head_dim == 128 || head_dim == 64) && attn_split_shape(n_kv); }
-size_t attn_decode_part_bytes(int64_t hsv, int64_t n_kv, int64_t n_head, int64_t T) {     // 0: no split for this shape
-    if (n_kv < attn_split_min(false) || n_kv % 32 != 0) return 0;
-    const int64_t ns = (n_kv + 127)/128 < 32 ? (n_kv + 127)/128 : 32;
-    return (size_t) T*n_head*ns*(hsv + 2)*4;
-}
-// the row-major-V kernel's [256/(hsv/8)][hsv] partial sums behind the scores
-static size_t attn_red_bytes(int64_t hsv) { return (size_t)(256/(hsv/8))*hsv*4; }
-
-// FLASH_ATTN_EXT: the (K, V) head sizes with a kernel. 80 is not a multiple of a 32-element block: F16 / BF16 caches only (the host pads a quantized cache to 96).
-bool attn_fa_head_sizes(int64_t hsk, int64_t hsv, int k_type, int v_type) {
-    if (hsk == 192 && hsv == 128) return true;
-    if (hsk != hsv) return false;
-    if (hsk == 80) return (k_type == T_F16 || k_type == T_BF16) && (v_type == T_F16 || v_type == T_BF16);
-    return hsk == 64 || hsk == 96 || hsk == 128 || hsk == 192 || hsk == 256;
-}
-bool attn_fa_supported(int64_t hsk, int64_t hsv, int k_type, int v_type, int64_t n_kv, int64_t n_head, int64_t T, size_t part_bytes) {
-    if (!attn_fa_head_sizes(hsk, hsv, k_type, v_type)) return false;
-    if (T > 8) return n_kv % 32 == 0 && n_kv > 0;
-    // few tokens: the whole score row in LDS, or the cell ranges through the partial-result buffer
-    return attn_one_wg_shape(n_kv) || (attn_split_shape(n_kv) && attn_decode_part_bytes(hsv, n_kv, n_head, T) <= part_bytes);
-}
-
-// which (K, V) type pairs the row-major-V (flash attention) kernel reads directly; the others go through kv_to_f16 first
-bool attn_decode_kv_types_fused(int k_type, int v_type) {
-    return (k_type == v_type && (k_type == T_F16 || k_type == T_Q8_0 || k_type == T_Q4_0 || k_type == T_BF16)) || (k_type == T_Q8_0 && (v_type == T_F16 || v_type == T_Q4_0));
-}
-// ALiBi slopes (ggml_compute_forward_flash_attn_ext_f16 / soft_max: m0 = 2^(-max_bias / n), m1 = 2^(-max_bias / 2 / n), n = 2^floor(log2 n_head))
-void attn_alibi(float max_bias, int64_t n_head, float & m0, float & m1, int & n_head_log2) {
-    n_head_log2 = 1; while (2*n_head_log2 <= (int) n_head) n_head_log2 *= 2;
-    m0 = powf(2.0f, -max_bias/(float) n_head_log2); m1 = powf(2.0f, -(max_bias/2.0f)/(float) n_head_log2);
-}
-
-void attn_decode(const void * q, size_t q_nb1, size_t q_nb2, const void * k, size_t k_nb1, size_t k_nb2, const void * v, size_t v_nb1, size_t v_nb2,
-                 const void * mask, size_t m_nb1, bool mask_f16, const float * sinks, float * dst, size_t dst_nb1,
-                 int64_t head_dim, int64_t n_kv, int64_t n_head, int64_t n_head_kv, int64_t T, float scale, hipStream_t stream, bool v_trans,
-                 float * part, size_t part_bytes, bool k_q8_0, const attn_extra * ex) {
-    attn_args a = { (const char *) q, q_nb1, q_nb2, (const char *) k, k_nb1, k_nb2, (const char *) v, v_nb1, v_nb2,
-                    (const char *) mask, m_nb1, mask_f16 ? 1 : 0, sinks, dst, dst_nb1, (int) n_kv, (int) n_head, (int) n_head_kv, (int) T, scale, 0, 1, nullptr };
-    a.softcap = 0.0f; a.max_bias = 0.0f; a.m0 = a.m1 = 1.0f; a.n_head_log2 = 1;
-    int kt = k_q8_0 ? T_Q8_0 : T_F16, vy = T_F16;
-    if (ex) {
-        attn_alibi(ex->max_bias, n_head, a.m0, a.m1, a.n_head_log2);
-        a.softcap = ex->softcap; a.max_bias = ex->max_bias;
-        if (ex->softcap != 0.0f) a.scale = scale/ex->softcap;
-        if (ex->k_type) kt = ex->k_type;
-        if (ex->v_type) vy = ex->v_type;
-    }
-    if (v_trans ? !((kt == T_F16 || kt == T_Q8_0) && vy == T_F16) : !attn_decode_kv_types_fused(kt, vy)) { fprintf(stderr, "attn_decode: KV types (%d, %d) have no kernel\n", kt, vy); abort(); }
-    const int64_t hsv = ex && ex->hsv ? ex->hsv : head_dim;
-    if (v_trans ? !(hsv == head_dim && (head_dim == 64 || head_dim == 128)) : !attn_fa_head_sizes(head_dim, hsv, kt, vy)) {
-        fprintf(stderr, "attn_decode: head sizes (%lld, %lld) have no kernel\n", (long long) head_dim, (long long) hsv); abort();
-    }
-    // long contexts: one workgroup per (head, token) walks every cell alone — 32 workgroups on 256 CUs. With a partial buffer the cells
-    // are split into ranges of >= 256 (at most 32 ranges) that run side by side and a small second kernel merges them.
-    static const bool split_on = env_on("GGML_MI355X_ATTN_SPLIT");
-    const size_t need = attn_decode_part_bytes(hsv, n_kv, n_head, T);
+attn_decode_plan attn_plan_decode(const attn_call & c) {
+    static const bool split_on = env_on("GGML_MI355X_ATTN_SPLIT"), live_on = env_on("GGML_MI355X_ATTN_LIVE_SCAN");
+    attn_decode_plan pl = {}; pl.nsplit = 1;
+    const bool kernel = c.q_type == T_F32 && c.n_head_kv > 0 && c.n_head % c.n_head_kv == 0 &&
+        (c.v_trans ? (c.k_type == T_F16 || c.k_type == T_Q8_0) && c.v_type == T_F16 && c.hsv == c.hsk && (c.hsk == 64 || c.hsk == 128)
+                   : attn_decode_kv_types_fused(c.k_type, c.v_type) && attn_fa_head_sizes(c.hsk, c.hsv, c.k_type, c.v_type));
+    if (!kernel) return pl;
+    // The threshold is asked for in three ways, kept as they were:
+    //  - part_bytes_needed counts from attn_split_min(false) on, for both layouts: between 256 and 383 cells it names, for transposed V, a need that the
+    //    split below never has. Harmless: it is only ever compared with the buffer, and the split asks for its own threshold as well.
+    //  - the split itself starts at attn_split_min(v_trans).
+    //  - a shape that works ONLY split (its score row is beyond one LDS) is accepted from attn_split_min(true) on, for row-major V too. As a difference this is
+    //    unreachable: such a shape has more than 12288 cells, above both defaults, and a set GGML_MI355X_ATTN_SPLIT_MIN gives both layouts the same value.
+    const int64_t n_kv = c.n_kv, ns = (n_kv + 127)/128 < 32 ? (n_kv + 127)/128 : 32;       // ranges of >= 128 cells, at most 32
+    if (n_kv >= attn_split_min(false) && n_kv % 32 == 0) pl.part_bytes_needed = (size_t) c.T*c.n_head*ns*(c.hsv + 2)*4;
+    const bool part_fits = pl.part_bytes_needed <= c.part_bytes;
+    // without a partial buffer the whole row of scores must fit the workgroup's LDS
+    pl.ok = (n_kv % 8 == 0 && n_kv*4 <= 48*1024) || (n_kv >= attn_split_min(true) && n_kv % 32 == 0 && part_fits);
     // row-major V (flash attention) at exactly the padding size: most cells of a short context are masked padding — one workgroup per head that stops at the last
     // live cell beats two ranges + a merge launch there (GGML_MI355X_ATTN_LIVE_SCAN=0: the split as before)
-    static const bool live_on = env_on("GGML_MI355X_ATTN_LIVE_SCAN");
-    const bool live_scan = live_on && !v_trans && mask && n_kv == 256 && T == 1;
-    a.live_scan = live_scan ? 1 : 0;
-    if (!live_scan && part && need && need <= part_bytes && n_kv >= attn_split_min(v_trans) && (split_on || n_kv*4 > 48*1024)) {
-        int64_t ns = (n_kv + 127)/128 < 32 ? (n_kv + 127)/128 : 32;       // ranges of >= 128 cells
-        const int64_t chunk = ((n_kv + ns - 1)/ns + 31)/32*32;          // the KV cache pads n_kv to 32 (256 with flash attention)
-        ns = (n_kv + chunk - 1)/chunk;
-        a.kv_chunk = (int) chunk; a.nsplit = (int) ns; a.part = part;
+    pl.live_scan = live_on && !c.v_trans && c.mask_type != T_NONE && n_kv == 256 && c.T == 1;
+    // long contexts: one workgroup per (head, token) walks every cell alone — 32 workgroups on 256 CUs. With a partial buffer the cells
+    // are split into ranges that run side by side and a small second kernel merges them.
+    if (!pl.live_scan && pl.part_bytes_needed && part_fits && n_kv >= attn_split_min(c.v_trans) && (split_on || n_kv*4 > 48*1024)) {
+        pl.kv_chunk = (int)(((n_kv + ns - 1)/ns + 31)/32*32);          // the KV cache pads n_kv to 32 (256 with flash attention)
+        pl.nsplit = (int)((n_kv + pl.kv_chunk - 1)/pl.kv_chunk);
     }
-    const dim3 grid((unsigned) n_head, (unsigned) T, (unsigned) a.nsplit);
-    const size_t lds = (((size_t)(a.nsplit > 1 ? a.kv_chunk : n_kv)*4 + 15) & ~(size_t) 15) + (v_trans ? 0 : attn_red_bytes(hsv));
-    if (lds > 64*1024) { fprintf(stderr, "attn_decode: %zu bytes of LDS for n_kv %lld\n", lds, (long long) n_kv); abort(); }      // (shapes attn_fa_supported / attn_decode_supported turn away)
-    if (!v_trans) {
-        // the (hsk, hsv) pairs of attn_fa_head_sizes, one instantiation each; 80: F16 / BF16 only
-#define MI_AD1(HK_, HV_, KT_, VY_) hipLaunchKernelGGL((k_attn_decode<HK_, false, KT_, VY_, HV_>), grid, dim3(256), lds, stream, a)
-#define MI_AD(KT_, VY_) do { if (head_dim == 128)      MI_AD1(128, 128, KT_, VY_); \
-                             else if (head_dim == 64)  MI_AD1(64, 64, KT_, VY_); \
-                             else if (head_dim == 96)  MI_AD1(96, 96, KT_, VY_); \
-                             else if (head_dim == 256) MI_AD1(256, 256, KT_, VY_); \
-                             else if (hsv == 192)      MI_AD1(192, 192, KT_, VY_); \
-                             else                      MI_AD1(192, 128, KT_, VY_); } while (0)
-        if (head_dim == 80) { if (kt == T_F16) MI_AD1(80, 80, T_F16, T_F16); else MI_AD1(80, 80, T_BF16, T_BF16); }
-        else if (kt == T_F16 && vy == T_F16)   MI_AD(T_F16, T_F16);
-        else if (kt == T_Q8_0 && vy == T_Q8_0) MI_AD(T_Q8_0, T_Q8_0);
-        else if (kt == T_Q4_0 && vy == T_Q4_0) MI_AD(T_Q4_0, T_Q4_0);
-        else if (kt == T_BF16 && vy == T_BF16) MI_AD(T_BF16, T_BF16);
-        else if (kt == T_Q8_0 && vy == T_F16)  MI_AD(T_Q8_0, T_F16);
-        else                                   MI_AD(T_Q8_0, T_Q4_0);
-#undef MI_AD
-#undef MI_AD1
+    // the scores of a workgroup's cells, and behind them the row-major-V kernel's [256/(hsv/8)][hsv] partial sums
+    pl.lds_bytes = (((size_t)(pl.nsplit > 1 ? pl.kv_chunk : n_kv)*4 + 15) & ~(size_t) 15) + (c.v_trans ? 0 : (size_t)(256/(c.hsv/8))*c.hsv*4);
+    return pl;
+}
+
+void attn_decode(const attn_call & c) {
+    const attn_decode_plan pl = attn_plan_decode(c);
+    if (!pl.ok || pl.lds_bytes > 64*1024 || (pl.nsplit > 1 && !c.part)) {
+        fprintf(stderr, "attn_decode: no kernel for head sizes (%lld, %lld), KV types (%d, %d), %lld cells (%zu bytes of LDS)\n", (long long) c.hsk, (long long) c.hsv, c.k_type, c.v_type, (long long) c.n_kv, pl.lds_bytes);
+        abort();
     }
-    if (v_trans && kt == T_Q8_0) {
-        if (head_dim == 128) hipLaunchKernelGGL((k_attn_decode<128, true, T_Q8_0>), grid, dim3(256), lds, stream, a);
-        else                 hipLaunchKernelGGL((k_attn_decode<64, true, T_Q8_0>),  grid, dim3(256), lds, stream, a);
-    } else
-    if (v_trans) {
-        if (head_dim == 128) hipLaunchKernelGGL((k_attn_decode<128>), grid, dim3(256), lds, stream, a);
-        else                 hipLaunchKernelGGL((k_attn_decode<64>),  grid, dim3(256), lds, stream, a);
-    }
-    if (a.nsplit > 1) {
-        const dim3 mg((unsigned) n_head, (unsigned) T);
-        switch (hsv) {
-            case 128: hipLaunchKernelGGL((k_attn_merge<128>), mg, dim3(128), 0, stream, a); break;
-            case 64:  hipLaunchKernelGGL((k_attn_merge<64>),  mg, dim3(64),  0, stream, a); break;
-            case 80:  hipLaunchKernelGGL((k_attn_merge<80>),  mg, dim3(80),  0, stream, a); break;
-            case 96:  hipLaunchKernelGGL((k_attn_merge<96>),  mg, dim3(96),  0, stream, a); break;
-            case 192: hipLaunchKernelGGL((k_attn_merge<192>), mg, dim3(192), 0, stream, a); break;
-            default:  hipLaunchKernelGGL((k_attn_merge<256>), mg, dim3(256), 0, stream, a); break;
+    attn_args a = {};
+    a.q = (const char *) c.q; a.q_nb1 = c.q_nb1; a.q_nb2 = c.q_nb2;
+    a.k = (const char *) c.k; a.k_nb1 = c.k_nb1; a.k_nb2 = c.k_nb2;
+    a.v = (const char *) c.v; a.v_nb1 = c.v_nb1; a.v_nb2 = c.v_nb2;
+    if (c.mask_type != T_NONE) { a.mask = (const char *) c.mask; a.m_nb1 = c.m_nb1; a.mask_f16 = c.mask_type == T_F16; }
+    a.sinks = c.sinks; a.dst = c.dst; a.dst_nb1 = c.dst_nb1;
+    a.n_kv = (int) c.n_kv; a.n_head = (int) c.n_head; a.n_head_kv = (int) c.n_head_kv; a.T = (int) c.T;
+    attn_set_softmax(a, c);
+    a.kv_chunk = pl.kv_chunk; a.nsplit = pl.nsplit; a.part = pl.nsplit > 1 ? c.part : nullptr; a.live_scan = pl.live_scan;
+    const dim3 grid((unsigned) c.n_head, (unsigned) c.T, (unsigned) pl.nsplit);
+    attn_dispatch_sizes(c.hsk, c.hsv, [&](auto hk, auto hv) {
+        constexpr int HK = decltype(hk)::value, HV = decltype(hv)::value;
+        if (!c.v_trans) attn_dispatch_types(c.k_type, c.v_type, [&](auto kt, auto vt) {
+            constexpr int KT = decltype(kt)::value, VY = decltype(vt)::value;
+            if constexpr (attn_fa_head_sizes(HK, HV, KT, VY)) hipLaunchKernelGGL((k_attn_decode<HK, false, KT, VY, HV>), grid, dim3(256), pl.lds_bytes, c.stream, a);
+        });
+        else if constexpr (HK == HV && (HK == 64 || HK == 128)) {
+            if (c.k_type == T_Q8_0) hipLaunchKernelGGL((k_attn_decode<HK, true, T_Q8_0>), grid, dim3(256), pl.lds_bytes, c.stream, a);
+            else                    hipLaunchKernelGGL((k_attn_decode<HK>), grid, dim3(256), pl.lds_bytes, c.stream, a);
         }
-    }
+        if (pl.nsplit > 1) hipLaunchKernelGGL((k_attn_merge<HV>), dim3((unsigned) c.n_head, (unsigned) c.T), dim3(HV), 0, c.stream, a);
+    });
 }
 
 } // namespace mi355x

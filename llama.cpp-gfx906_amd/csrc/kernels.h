@@ -9,7 +9,9 @@
 #pragma once
 
 #include <hip/hip_runtime.h>
+#include <math.h>
 #include <stdint.h>
+#include <type_traits>
 
 #include "env_switch.h"
 
@@ -205,42 +207,73 @@ void swiglu_quant(const float * g, size_t g_stride, const float * u, size_t u_st
 // SET_ROWS(k) + SET_ROWS(v, element scatter) into the f16 cache, one launch
 void kv_store_f16(const float * k_src, size_t k_src_nb1, const int64_t * k_idx, void * k_dst, size_t k_dst_nb1, int64_t k_ne0, int64_t k_rows,
                   const float * v_src, const int64_t * v_idx, void * v_dst, int64_t v_n, hipStream_t stream);
-// K.q -> softmax -> V^T.p -> [hd*n_head, T] for T query tokens over the f16 cache
-// FLASH_ATTN_EXT's remaining parameters: logit_softcap, max_bias (ALiBi), the cache's element types (0 = F16) and V's head size (0 = K's)
-struct attn_extra { float softcap, max_bias; int k_type, v_type; int hsv; };
-// FLASH_ATTN_EXT's (K, V) head sizes: 64/64, 80/80 (F16 / BF16 caches only), 96/96, 128/128, 192/192, 256/256 and 192/128
-bool attn_fa_head_sizes(int64_t hsk, int64_t hsv, int k_type, int v_type);
+// ---- attention: K.q -> soft_max(scale, mask, sinks) -> V.p -> [hsv*n_head, T]; a few tokens (T <= 8): decode_fused.hip, many: attn_prefill.hip ----
+// FLASH_ATTN_EXT's (K, V) head sizes: 64/64, 80/80 (not a multiple of a 32-element block: F16 / BF16 caches only), 96/96, 128/128, 192/192, 256/256 and 192/128
+constexpr bool attn_fa_head_sizes(int64_t hsk, int64_t hsv, int k_type, int v_type) {
+    if (hsk == 192 && hsv == 128) return true;
+    if (hsk != hsv) return false;
+    if (hsk == 80) return (k_type == T_F16 || k_type == T_BF16) && (v_type == T_F16 || v_type == T_BF16);
+    return hsk == 64 || hsk == 96 || hsk == 128 || hsk == 192 || hsk == 256;
+}
+// the (K, V) type pairs the row-major-V decode kernel reads directly; the others go through kv_to_f16 first
+constexpr bool attn_decode_kv_types_fused(int k_type, int v_type) {
+    return (k_type == v_type && (k_type == T_F16 || k_type == T_Q8_0 || k_type == T_Q4_0 || k_type == T_BF16)) || (k_type == T_Q8_0 && (v_type == T_F16 || v_type == T_Q4_0));
+}
 // the decode attention's partial-result buffer: 8 tokens x 128 heads x 32 ranges x (128 + 2) floats, i.e. 64 heads of 256 (+ 2); allocated once per backend
 constexpr size_t ATTN_PART_BYTES = (size_t) 8*128*32*(128 + 2)*4;
-// the one answer for supports_op (part_bytes = ATTN_PART_BYTES) and the node itself (the buffer it has): head sizes as attn_fa_head_sizes; T > 8: n_kv % 32 == 0;
-// T <= 8: n_kv % 8 == 0 up to 12288 cells, beyond that n_kv % 32 == 0 and the cell ranges' partial results within part_bytes
-bool attn_fa_supported(int64_t hsk, int64_t hsv, int k_type, int v_type, int64_t n_kv, int64_t n_head, int64_t T, size_t part_bytes);
-bool attn_decode_kv_types_fused(int k_type, int v_type);      // read directly by the row-major-V decode kernel (others: kv_to_f16 first)
-void attn_alibi(float max_bias, int64_t n_head, float & m0, float & m1, int & n_head_log2);
+constexpr int T_NONE = -1;
+// one attention launch, as both launchers and every plan and support answer take it: value-initialise, fill by name (the plans read no pointer)
+struct attn_call {
+    const void * q; size_t q_nb1, q_nb2; int q_type;      // [hsk, T, n_head], T_F32: nb1 = token stride, nb2 = head stride
+    const void * k; size_t k_nb1, k_nb2; int k_type;      // [hsk, n_kv, n_head_kv]: nb1 = cell stride, nb2 = head stride
+    const void * v; size_t v_nb1, v_nb2; int v_type;      // row-major [hsv, n_kv, n_head_kv]: nb1 = cell stride; v_trans [n_kv, hsv, n_head_kv]: nb1 = dim stride (a row over cells)
+    bool v_trans;                                         // the V cache of the graph without flash attention, and kv_to_f16's transposed copy
+    const void * mask; size_t m_nb1; int mask_type = T_NONE;      // [n_kv, >= T] of T_F16 / T_F32, or T_NONE
+    const float * sinks;
+    float * dst; size_t dst_nb1;                          // [hsv*n_head, T]; NULL (prefill): only y16 is wanted
+    uint16_t * y16;                                       // prefill: also the bf16 copy the following mat-mul reads, rows of hsv*n_head rounded up to a multiple of 64
+    int64_t hsk, hsv, n_kv, n_head, n_head_kv, T;
+    float scale, softcap, max_bias;                       // logit_softcap and ALiBi: FLASH_ATTN_EXT's other two parameters (0: none)
+    float * part; size_t part_bytes;                      // decode: the partial-result buffer on offer (0 bytes: none)
+    hipStream_t stream;
+};
+// Decode, planned once. Long contexts (a multiple of 32 cells): with the partial buffer the cells are split into nsplit ranges of kv_chunk (up to 32 workgroups per
+// (head, token)) that a second small kernel merges; live_scan: one workgroup per head that stops at the last unmasked cell. ok: there is a kernel for the
+// head sizes and types (v_trans: 64 / 128, F16 or Q8_0 K, F16 V; row-major V: attn_fa_head_sizes, attn_decode_kv_types_fused) and the score row fits the LDS
+// (n_kv % 8 == 0 up to 12288 cells) or its ranges fit part_bytes. part_bytes_needed: 0 = no split for this shape.
+struct attn_decode_plan { bool ok; int nsplit, kv_chunk; bool live_scan; size_t lds_bytes, part_bytes_needed; };
+attn_decode_plan attn_plan_decode(const attn_call & c);
+// Prefill: one wave per (head, 32 queries), nw waves per workgroup = hpw heads of one kv head x query tiles x ks-way split cell blocks. ok: F16 K and V, n_kv % 32 == 0,
+// head sizes: v_trans: attn_fa_head_sizes; row-major V: 64 / 128
+struct attn_prefill_plan { bool ok; int nw, hpw, ks; dim3 grid; };
+attn_prefill_plan attn_plan_prefill(const attn_call & c);
+// the one support answer, for supports_op (part_bytes = ATTN_PART_BYTES) and the nodes themselves (the buffer they have): the plan's ok for the operands as
+// the launcher gets them — FLASH_ATTN_EXT's after fa_kv16_plan's conversions (backend_nodes.cpp)
+inline bool attn_supported(const attn_call & c) { return c.T > 8 ? attn_plan_prefill(c).ok : attn_plan_decode(c).ok; }
+void attn_decode(const attn_call & c);       // T <= 8
+void attn_prefill(const attn_call & c);      // T > 8
 // K / V cache views [hd, n_kv, n_head_kv] of type F16 / BF16 / Q8_0 / Q4_0 -> dense f16: rows of cells [n_head_kv][n_kv][hd], or transposed
 // (rows over cells, the layout the matrix-core prefill kernel stages with coalesced loads) [n_head_kv][hd][n_kv]; n_kv % 8 == 0; hd (the size of the tensor
 // converted, K's or V's): a multiple of 8 (of 32 for Q8_0 / Q4_0) up to 256
 void kv_to_f16(int type, const void * src, size_t nb1, size_t nb2, int64_t hd, int64_t n_kv, int64_t n_head_kv, uint16_t * dst, bool transpose, hipStream_t stream);
-bool attn_decode_supported(int64_t head_dim, int64_t n_kv);      // head size 64 / 128 (the graph without flash attention)
-// head_dim: K's head size; v_trans: 64 / 128; row-major V: the pairs of attn_fa_head_sizes, V's size in ex->hsv
-void attn_decode(const void * q, size_t q_nb1, size_t q_nb2, const void * k, size_t k_nb1, size_t k_nb2, const void * v, size_t v_nb1, size_t v_nb2,
-                 const void * mask, size_t m_nb1, bool mask_f16, const float * sinks, float * dst, size_t dst_nb1,
-                 int64_t head_dim, int64_t n_kv, int64_t n_head, int64_t n_head_kv, int64_t T, float scale, hipStream_t stream, bool v_trans = true,
-                 float * part = nullptr, size_t part_bytes = 0, bool k_q8_0 = false,      // k_q8_0: K rows are Q8_0 blocks (transposed-V form only)
-                 const attn_extra * ex = nullptr);
-// long contexts (n_kv >= 384, or 256 with row-major V; a multiple of 32; GGML_MI355X_ATTN_SPLIT_MIN): with a partial buffer of attn_decode_part_bytes() the cells are split over up to 32 workgroups per
-// (head, token) and merged by a second small kernel; attn_decode_supported_split: shapes that only work with the buffer (scores beyond one LDS)
-size_t attn_decode_part_bytes(int64_t hsv, int64_t n_kv, int64_t n_head, int64_t T);      // hsv: V's head size (any the kernels take)
-bool attn_decode_supported_split(int64_t head_dim, int64_t n_kv);      // head size 64 / 128
-// the same node group for many tokens (prefill): one wave per (head, 32 queries), scores and probabilities stay in registers
-// (attn_prefill.hip); n_kv % 32 == 0
-bool attn_prefill_supported(int64_t head_dim, int64_t n_kv);      // head size 64 / 128 (the graph without flash attention)
-// head_dim: K's head size; transposed V: the pairs of attn_fa_head_sizes, V's size in ex->hsv; row-major V: 64 / 128
-void attn_prefill(const void * q, size_t q_nb1, size_t q_nb2, const void * k, size_t k_nb1, size_t k_nb2, const void * v, size_t v_nb1, size_t v_nb2,
-                  const void * mask, size_t m_nb1, bool mask_f16, const float * sinks, float * dst, size_t dst_nb1,
-                  int64_t head_dim, int64_t n_kv, int64_t n_head, int64_t n_head_kv, int64_t T, float scale, hipStream_t stream, bool v_trans = true,
-                  uint16_t * y16 = nullptr,      // y16 != NULL: also (dst == NULL: only) the bf16 copy the following mat-mul reads, rows of hsv*n_head (rounded up to a multiple of 64)
-                  const attn_extra * ex = nullptr);     // (K and V are f16 here: other cache types are converted by kv_to_f16 first)
+// the soft_max's constants as both kernels' argument structs carry them: the scale divided by logit_softcap, and ALiBi's slopes
+// (ggml_compute_forward_flash_attn_ext_f16 / soft_max: m0 = 2^(-max_bias / n), m1 = 2^(-max_bias / 2 / n), n = 2^floor(log2 n_head))
+template <typename A> static inline void attn_set_softmax(A & a, const attn_call & c) {
+    a.scale = c.softcap != 0.0f ? c.scale/c.softcap : c.scale; a.softcap = c.softcap; a.max_bias = c.max_bias;
+    a.n_head_log2 = 1; while (2*a.n_head_log2 <= (int) c.n_head) a.n_head_log2 *= 2;
+    a.m0 = powf(2.0f, -c.max_bias/(float) a.n_head_log2); a.m1 = powf(2.0f, -(c.max_bias/2.0f)/(float) a.n_head_log2);
+}
+// the instantiations: f(K, V) with the matching pair as two std::integral_constant (as mmq_dispatch_type, mmq.hip); false: no such pair
+template <int A, int B, typename F> static inline bool attn_pair_is(int64_t a, int64_t b, F & f) { return a == A && b == B && (f(std::integral_constant<int, A>{}, std::integral_constant<int, B>{}), true); }
+template <typename F> static inline bool attn_dispatch_sizes(int64_t hsk, int64_t hsv, F && f) {      // the pairs of attn_fa_head_sizes
+    return attn_pair_is<64, 64>(hsk, hsv, f) || attn_pair_is<80, 80>(hsk, hsv, f) || attn_pair_is<96, 96>(hsk, hsv, f) || attn_pair_is<128, 128>(hsk, hsv, f) ||
+           attn_pair_is<192, 192>(hsk, hsv, f) || attn_pair_is<256, 256>(hsk, hsv, f) || attn_pair_is<192, 128>(hsk, hsv, f);
+}
+template <typename F> static inline bool attn_dispatch_types(int k_type, int v_type, F && f) {      // the pairs of attn_decode_kv_types_fused
+    return attn_pair_is<T_F16, T_F16>(k_type, v_type, f) || attn_pair_is<T_Q8_0, T_Q8_0>(k_type, v_type, f) || attn_pair_is<T_Q4_0, T_Q4_0>(k_type, v_type, f) ||
+           attn_pair_is<T_BF16, T_BF16>(k_type, v_type, f) || attn_pair_is<T_Q8_0, T_F16>(k_type, v_type, f) || attn_pair_is<T_Q8_0, T_Q4_0>(k_type, v_type, f);
+}
+template <int... Vs, typename F> static inline bool attn_dispatch_int(int v, F && f) { return ((v == Vs && (f(std::integral_constant<int, Vs>{}), true)) || ...); }
 
 // the persistent kernels run one workgroup per CU: the current device's CU count, asked for once (mmvq_fused.hip)
 int device_cu_count();

@@ -545,6 +545,29 @@ def test_long_context_decode_attention_split(fa):
     assert orc.nmse(outs[0], outs[1]) <= 5e-4, orc.nmse(outs[0], outs[1])
 
 
+@pytest.mark.parametrize("type_k", [pytest.param(0, id="F16"), pytest.param(8, id="Q8_0")])
+def test_decode_attention_split_few_tokens(type_k):
+    """The transposed-V decode kernel (no flash attention) with its cells split into ranges, for an F16 and a Q8_0 K cache and for steps of 1, 1, 3 and 8
+    tokens: behind a 390-token prompt the cache view (padded to 32 cells) is 416-448 cells, above the 384-cell threshold, in four ranges. Fusion on
+    against the node-by-node path, per step; gates: the long-context test's 5e-4 (F16) and the quantized-K test's fused-versus-generic 2e-3 (Q8_0)."""
+    be = backend()
+    toks = np.random.default_rng(7).integers(0, 512, size=403).astype(np.int32)
+    outs = {}
+    for fusion in (1, 0):
+        be.set_option("fusion", fusion)
+        m = ls.SynthLlama(be, "tiny", "Q4_K_M", n_ctx=512, seed=9, type_k=type_k)
+        try:
+            m.decode(toks[:390])
+            outs[fusion] = [m.decode(toks[a:b]).copy() for a, b in ((390, 391), (391, 392), (392, 395), (395, 403))]
+        finally:
+            m.free()
+    be.set_option("fusion", 1)
+    errs = [float(orc.nmse(b_, a_)) for a_, b_ in zip(outs[1], outs[0])]
+    print("test_decode_attention_split_few_tokens type_k", type_k, "nmse per step", errs)
+    assert all(np.isfinite(a_).all() for a_ in outs[1])
+    assert max(errs) <= (2e-3 if type_k == 8 else 5e-4), errs
+
+
 def test_kv_clear_restarts_sequence():
     be = backend()
     m = ls.SynthLlama(be, "tiny", "Q4_K_M", n_ctx=64, seed=9)
