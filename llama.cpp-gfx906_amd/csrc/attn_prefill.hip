@@ -35,6 +35,7 @@ struct attn_pf_args {
     int n_kv, n_head, n_head_kv, T;
     float scale;
     float softcap, max_bias, m0, m1; int n_head_log2;      // logit_softcap (scale already divided by it) and ALiBi, as in decode_fused.hip
+    size_t q_nb3, k_nb3, v_nb3, m_nb3, dst_nb3;            // blockIdx.z = the KV stream (kernels.h: attn_call): its q, K, V, mask (m_nb3 = 0: shared) and T result rows
 };
 
 static __device__ __forceinline__ float xhalf(float v, int lane) {      // the value lane ^ 32 holds
@@ -59,7 +60,15 @@ constexpr int APF_KLD = 16;     // LDS row padding (bytes): K rows HD*2 + 16 (ds
 // NW: waves per workgroup. 192 and 256 run with 4: their accumulators (NDT x 16) and Q (NC x 4 registers) need more than the 256 registers a lane has
 // when two waves share a SIMD.
 template <int HD, bool VT, int MASK, int KS, int HDV = HD, int NW = APF_NW>
-__global__ void __launch_bounds__(64*NW) k_attn_prefill(const attn_pf_args p, int hpw) {
+__global__ void __launch_bounds__(64*NW) k_attn_prefill(const attn_pf_args pa, int hpw) {
+    attn_pf_args p = pa;      // this workgroup's stream (all zero offsets in a one-stream launch)
+    {
+        const size_t sz = blockIdx.z;
+        p.q += sz*pa.q_nb3; p.k += sz*pa.k_nb3; p.v += sz*pa.v_nb3;
+        if (pa.mask) p.mask += sz*pa.m_nb3;
+        if (pa.dst) p.dst = (float *) ((char *) pa.dst + sz*pa.dst_nb3);
+        if (pa.y16) p.y16 += sz*(size_t) pa.T*pa.kp16;
+    }
     constexpr int NC = HD/16, NDT = (HDV + 31)/32, CPR = HD/8, NT = 64*NW;      // CPR: 16-byte chunks per K row
     constexpr int HDVP = 32*NDT;                                        // V^T rows in LDS
     constexpr int KROW = HD*2 + APF_KLD, VROW = 64 + 8, KBLK = 32*KROW, VBLK = HDVP*VROW;
@@ -303,12 +312,14 @@ __global__ void __launch_bounds__(64*NW) k_attn_prefill(const attn_pf_args p, in
 attn_prefill_plan attn_plan_prefill(const attn_call & c) {
     static const bool ks4_on = env_on("GGML_MI355X_ATTN_PF_KS4");
     attn_prefill_plan pl = {};
-    pl.ok = c.q_type == T_F32 && c.k_type == T_F16 && c.v_type == T_F16 && c.n_kv % 32 == 0 && c.n_kv > 0 && c.n_head_kv > 0 && c.n_head % c.n_head_kv == 0 &&
+    pl.ok = c.q_type == T_F32 && c.k_type == T_F16 && c.v_type == T_F16 && c.n_kv % 32 == 0 && c.n_kv > 0 && c.n_head_kv > 0 && c.n_head % c.n_head_kv == 0 && attn_n_stream(c) <= 65535 &&
             (c.v_trans ? attn_fa_head_sizes(c.hsk, c.hsv, T_F16, T_F16) : c.hsv == c.hsk && (c.hsk == 64 || c.hsk == 128));
     if (!pl.ok) return pl;
     pl.nw = c.hsk > 128 ? 4 : APF_NW;                                       // waves per workgroup (the kernel's NW)
     const int64_t R = c.n_head/c.n_head_kv, T = c.T;
     pl.hpw = R % 8 == 0 && pl.nw >= 8 ? 8 : R % 4 == 0 ? 4 : R % 2 == 0 ? 2 : 1;          // heads of one kv head per workgroup
+    // (the workgroup counts below are ONE stream's: a launch of several streams keeps the one-stream plan, and with it the one-stream launch's bits; whether the cell
+    // split still pays once the streams fill the chip is not measured)
     // few workgroups (short prompts): the waves of a (head, query tile) split the cell blocks of an iteration two or four ways, shortening the loop that is the critical path
     const int64_t wgs1 = ((T + 32*(pl.nw/pl.hpw) - 1)/(32*(pl.nw/pl.hpw)))*(c.n_head/pl.hpw);
     pl.ks = (pl.hpw*2 <= pl.nw && pl.hpw <= 4 && wgs1 < 160 && c.n_kv >= 128) ? 2 : 1;
@@ -318,7 +329,7 @@ attn_prefill_plan attn_plan_prefill(const attn_call & c) {
         if (wgs2 < 200) { pl.hpw = 2; pl.ks = 4; }
     }
     const int qpw = pl.nw/(pl.hpw*pl.ks);                                            // query tiles per workgroup
-    pl.grid = dim3((unsigned)((T + 32*qpw - 1)/(32*qpw)), (unsigned)(c.n_head/pl.hpw));
+    pl.grid = dim3((unsigned)((T + 32*qpw - 1)/(32*qpw)), (unsigned)(c.n_head/pl.hpw), (unsigned) attn_n_stream(c));
     return pl;
 }
 
@@ -347,6 +358,7 @@ void attn_prefill(const attn_call & c) {
     if (c.mask_type != T_NONE) { a.mask = (const char *) c.mask; a.m_nb1 = c.m_nb1; a.mask_f16 = c.mask_type == T_F16; }
     a.sinks = c.sinks; a.dst = c.dst; a.dst_nb1 = c.dst_nb1; a.y16 = c.y16; a.kp16 = (int)((c.hsv*c.n_head + 63) & ~(int64_t) 63);
     a.n_kv = (int) c.n_kv; a.n_head = (int) c.n_head; a.n_head_kv = (int) c.n_head_kv; a.T = (int) c.T;
+    if (c.n_stream > 1) { a.q_nb3 = c.q_nb3; a.k_nb3 = c.k_nb3; a.v_nb3 = c.v_nb3; a.m_nb3 = c.m_nb3; a.dst_nb3 = c.dst_nb3; }
     attn_set_softmax(a, c);
     // the (hsk, hsv) pairs of attn_fa_head_sizes x the mask's kind (0 = none, 1 = f32, 2 = f16) x the plan's ks, one instantiation each
     attn_dispatch_sizes(c.hsk, c.hsv, [&](auto hk, auto hv) { attn_dispatch_int<0, 1, 2>(c.mask_type == T_NONE ? 0 : c.mask_type == T_F16 ? 2 : 1, [&](auto mk) { attn_dispatch_int<1, 2, 4>(pl.ks, [&](auto ks) {
@@ -357,15 +369,17 @@ void attn_prefill(const attn_call & c) {
 }
 
 // ---- the cache as the kernels above want it: f16, cells as rows or transposed (kv_types.h has the element types) ----
-struct kvc_args { const char * src; size_t nb1, nb2; int hd, n_kv, n_head_kv; uint16_t * dst; };
+// n_heads = n_head_kv*n_stream rows of cells: head index hs = stream*n_head_kv + kv head, the order of the dense copy
+struct kvc_args { const char * src; size_t nb1, nb2, nb3; int hd, n_kv, n_head_kv, n_heads; uint16_t * dst; };
+static __device__ __forceinline__ const char * kvc_head(const kvc_args & p, int hs) { return p.src + (size_t)(hs % p.n_head_kv)*p.nb2 + (size_t)(hs / p.n_head_kv)*p.nb3; }
 template <int TY>
 __global__ void __launch_bounds__(256) k_kv_rows_f16(const kvc_args p) {
     const int c8 = p.hd >> 3;
-    const long long e = (long long) blockIdx.x*256 + threadIdx.x, tot = (long long) p.n_head_kv*p.n_kv*c8;
+    const long long e = (long long) blockIdx.x*256 + threadIdx.x, tot = (long long) p.n_heads*p.n_kv*c8;
     if (e >= tot) return;
     const int sub = (int)(e % c8); const long long cj = e / c8; const int j = (int)(cj % p.n_kv), hk = (int)(cj / p.n_kv);
     float f[8];
-    kv_cvt8<TY>(kv_raw8<TY>(p.src + (size_t) hk*p.nb2 + (size_t) j*p.nb1, sub), sub, f);
+    kv_cvt8<TY>(kv_raw8<TY>(kvc_head(p, hk) + (size_t) j*p.nb1, sub), sub, f);
     uint32_t w[4];
 #pragma unroll
     for (int i = 0; i < 4; i++) w[i] = (uint32_t) f32_to_f16_bits(f[2*i]) | ((uint32_t) f32_to_f16_bits(f[2*i + 1]) << 16);
@@ -378,10 +392,11 @@ __global__ void __launch_bounds__(256) k_kv_trans_f16(const kvc_args p) {
     constexpr int LROW = 64 + 8;       // halves per LDS row (16-byte aligned rows)
     __shared__ __attribute__((aligned(16))) uint16_t tile[128*LROW];
     const int hk = blockIdx.y, j0 = blockIdx.x*64, d0 = blockIdx.z*128, c8 = min(p.hd - d0, 128) >> 3;      // c8: the slab's 8-dim chunks
+    const char * src_h = kvc_head(p, hk);
     for (int e = threadIdx.x; e < 64*c8; e += 256) {
         const int cell = e / c8, sub = e % c8, j = min(j0 + cell, p.n_kv - 1);
         float f[8];
-        kv_cvt8<TY>(kv_raw8<TY>(p.src + (size_t) hk*p.nb2 + (size_t) j*p.nb1, (d0 >> 3) + sub), (d0 >> 3) + sub, f);
+        kv_cvt8<TY>(kv_raw8<TY>(src_h + (size_t) j*p.nb1, (d0 >> 3) + sub), (d0 >> 3) + sub, f);
 #pragma unroll
         for (int i = 0; i < 8; i++) tile[(sub*8 + i)*LROW + cell] = f32_to_f16_bits(f[i]);
     }
@@ -391,13 +406,14 @@ __global__ void __launch_bounds__(256) k_kv_trans_f16(const kvc_args p) {
         if (j0 + g8*8 < p.n_kv) *(int4v *) (p.dst + ((size_t) hk*p.hd + d0 + d)*p.n_kv + j0 + g8*8) = *(const int4v *) (tile + d*LROW + g8*8);
     }
 }
-void kv_to_f16(int type, const void * src, size_t nb1, size_t nb2, int64_t hd, int64_t n_kv, int64_t n_head_kv, uint16_t * dst, bool transpose, hipStream_t stream) {
-    if (hd % 8 || hd < 8 || hd > 256 || ((type == T_Q8_0 || type == T_Q4_0) && hd % 32) || n_kv % 8 || n_kv < 8) { fprintf(stderr, "kv_to_f16: unsupported shape (hd %lld, n_kv %lld)\n", (long long) hd, (long long) n_kv); abort(); }
-    const kvc_args a = { (const char *) src, nb1, nb2, (int) hd, (int) n_kv, (int) n_head_kv, dst };
-    const long long tot = (long long) n_head_kv*n_kv*(hd/8);
+void kv_to_f16(int type, const void * src, size_t nb1, size_t nb2, size_t nb3, int64_t hd, int64_t n_kv, int64_t n_head_kv, int64_t n_stream, uint16_t * dst, bool transpose, hipStream_t stream) {
+    const int64_t n_heads = n_head_kv*(n_stream > 1 ? n_stream : 1);
+    if (hd % 8 || hd < 8 || hd > 256 || ((type == T_Q8_0 || type == T_Q4_0) && hd % 32) || n_kv % 8 || n_kv < 8 || n_heads > 65535) { fprintf(stderr, "kv_to_f16: unsupported shape (hd %lld, n_kv %lld)\n", (long long) hd, (long long) n_kv); abort(); }
+    const kvc_args a = { (const char *) src, nb1, nb2, nb3, (int) hd, (int) n_kv, (int) n_head_kv, (int) n_heads, dst };
+    const long long tot = (long long) n_heads*n_kv*(hd/8);
     if (!attn_dispatch_int<T_F16, T_BF16, T_Q8_0, T_Q4_0>(type, [&](auto ty) {
             constexpr int TY = decltype(ty)::value;
-            if (transpose) hipLaunchKernelGGL((k_kv_trans_f16<TY>), dim3((unsigned)((n_kv + 63)/64), (unsigned) n_head_kv, (unsigned)((hd + 127)/128)), dim3(256), 0, stream, a);
+            if (transpose) hipLaunchKernelGGL((k_kv_trans_f16<TY>), dim3((unsigned)((n_kv + 63)/64), (unsigned) n_heads, (unsigned)((hd + 127)/128)), dim3(256), 0, stream, a);
             else           hipLaunchKernelGGL((k_kv_rows_f16<TY>), dim3((unsigned)((tot + 255)/256)), dim3(256), 0, stream, a);
         })) { fprintf(stderr, "kv_to_f16: cache type %d is not supported\n", type); abort(); }
 }

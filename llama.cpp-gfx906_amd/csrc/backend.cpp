@@ -487,14 +487,17 @@ static bool mi_supports_op(const struct ggml_tensor * op) {
         case GGML_OP_FLASH_ATTN_EXT: {     // head sizes 64, 80, 96, 128, 192, 256 and 192/128 (attn_fa_head_sizes); K / V cache types F16, BF16, Q8_0, Q4_0; ALiBi and logit soft-cap (src/llama-graph.cpp:1245-1265)
             const struct ggml_tensor * k = op->src[1]; const struct ggml_tensor * v = op->src[2]; const struct ggml_tensor * mask = op->src[3];
             if (s0->type != GGML_TYPE_F32 || !fa_kv_type(k->type) || !fa_kv_type(v->type) || op->type != GGML_TYPE_F32) return false;
-            if (s0->ne[3] != 1 || k->ne[3] != 1 || v->ne[3] != 1 || s0->ne[0] != k->ne[0] || v->ne[1] != k->ne[1] || v->ne[2] != k->ne[2] || s0->ne[2] % k->ne[2] != 0) return false;
+            // per-sequence KV streams: q, K and V carry the same ne[3] (one cache stream per q batch; ggml's broadcast of one cache over several is refused)
+            if (s0->ne[3] != k->ne[3] || v->ne[3] != k->ne[3] || s0->ne[0] != k->ne[0] || v->ne[1] != k->ne[1] || v->ne[2] != k->ne[2] || s0->ne[2] % k->ne[2] != 0) return false;
             if (op_f32(op, 1) < 0.0f) return false;
-            if (mask && (mask->type != GGML_TYPE_F16 || mask->ne[2] != 1 || mask->ne[3] != 1 || mask->ne[0] != k->ne[1] || mask->ne[1] < s0->ne[1] || mask->nb[1] % 16)) return false;
+            if (mask && (mask->type != GGML_TYPE_F16 || mask->ne[2] != 1 || (mask->ne[3] != 1 && mask->ne[3] != s0->ne[3]) || mask->ne[0] != k->ne[1] || mask->ne[1] < s0->ne[1] || mask->nb[1] % 16 || mask->nb[3] % 16)) return false;
             if (op->nb[1] != (size_t) v->ne[0]*4) return false;
-            if (s0->nb[0] != 4 || k->nb[0] != ggml_type_size(k->type) || v->nb[0] != ggml_type_size(v->type) || s0->nb[1] % 16 || s0->nb[2] % 16) return false;
+            if (s0->nb[0] != 4 || k->nb[0] != ggml_type_size(k->type) || v->nb[0] != ggml_type_size(v->type) || s0->nb[1] % 16 || s0->nb[2] % 16 || s0->nb[3] % 16 || op->nb[3] % 16) return false;
             // (f16 rows are read 16 bytes at a time; block rows 2-byte aligned)
-            if (k->nb[1] % (k->type == GGML_TYPE_F16 || k->type == GGML_TYPE_BF16 ? 16 : 2) || k->nb[2] % (k->type == GGML_TYPE_F16 || k->type == GGML_TYPE_BF16 ? 16 : 2)) return false;
-            if (v->nb[1] % (v->type == GGML_TYPE_F16 || v->type == GGML_TYPE_BF16 ? 16 : 2) || v->nb[2] % (v->type == GGML_TYPE_F16 || v->type == GGML_TYPE_BF16 ? 16 : 2)) return false;
+            if (k->nb[1] % (k->type == GGML_TYPE_F16 || k->type == GGML_TYPE_BF16 ? 16 : 2) || k->nb[2] % (k->type == GGML_TYPE_F16 || k->type == GGML_TYPE_BF16 ? 16 : 2) ||
+                k->nb[3] % (k->type == GGML_TYPE_F16 || k->type == GGML_TYPE_BF16 ? 16 : 2)) return false;
+            if (v->nb[1] % (v->type == GGML_TYPE_F16 || v->type == GGML_TYPE_BF16 ? 16 : 2) || v->nb[2] % (v->type == GGML_TYPE_F16 || v->type == GGML_TYPE_BF16 ? 16 : 2) ||
+                v->nb[3] % (v->type == GGML_TYPE_F16 || v->type == GGML_TYPE_BF16 ? 16 : 2)) return false;
             // the head sizes, and the shapes: a few tokens' score row in LDS or their cell ranges through the fixed partial-result buffer; many tokens: 32-cell blocks
             return fa_kv16_plan(op, nullptr, nullptr, ATTN_PART_BYTES).ok;
         }

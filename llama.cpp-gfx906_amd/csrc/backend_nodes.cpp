@@ -43,7 +43,8 @@ void pass_end(mi_backend_ctx * c) {
 // FLASH_ATTN_EXT as its kernels get it: the dense f16 copies they need (kv_to_f16 into kv16, K first and V behind it) — the V cache transposed for the matrix-core
 // prefill kernel (always: rows over cells are what it stages with coalesced loads), K when it is not f16; for a few tokens only what the decode kernel does not read
 // directly (attn_decode_kv_types_fused) — and the launch's operands after them. ok: the cache's types have kernels at these head sizes and the launch has a plan
-// with the partial buffer on offer. kv16 may be NULL (supports_op, sizing kv16: nothing is launched from the result).
+// with the partial buffer on offer. kv16 may be NULL (supports_op, sizing kv16: nothing is launched from the result). Per-sequence KV streams (ne[3] of q, K and V):
+// one call for all of them; the copies hold every stream, each dense behind the previous one.
 fa_operands fa_kv16_plan(const struct ggml_tensor * n, void * kv16, float * part, size_t part_bytes) {
     const struct ggml_tensor * q = n->src[0]; const struct ggml_tensor * k = n->src[1]; const struct ggml_tensor * v = n->src[2];
     const struct ggml_tensor * mask = n->src[3]; const struct ggml_tensor * sinks = n->src[4];
@@ -57,17 +58,19 @@ fa_operands fa_kv16_plan(const struct ggml_tensor * n, void * kv16, float * part
     a.sinks = sinks ? (const float *) sinks->data : nullptr; a.dst = (float *) n->data; a.dst_nb1 = n->nb[2];
     a.scale = op_f32(n, 0); a.max_bias = op_f32(n, 1); a.softcap = op_f32(n, 2);
     a.part = part; a.part_bytes = part_bytes;
+    a.n_stream = q->ne[3]; a.q_nb3 = q->nb[3]; a.k_nb3 = k->nb[3]; a.v_nb3 = v->nb[3]; a.m_nb3 = mask && mask->ne[3] > 1 ? mask->nb[3] : 0; a.dst_nb3 = n->nb[3];
+    const size_t S = (size_t) attn_n_stream(a);
     const bool prefill = a.T > 8, direct = !prefill && attn_decode_kv_types_fused(a.k_type, a.v_type);
     if (!direct && k->type != GGML_TYPE_F16) {
-        p.k_bytes = (((size_t) a.hsk*a.n_kv*a.n_head_kv*2) + 255) & ~(size_t) 255;
-        a.k = kv16; a.k_nb1 = (size_t) a.hsk*2; a.k_nb2 = (size_t) a.n_kv*a.hsk*2; a.k_type = T_F16;
+        p.k_bytes = (((size_t) a.hsk*a.n_kv*a.n_head_kv*2*S) + 255) & ~(size_t) 255;
+        a.k = kv16; a.k_nb1 = (size_t) a.hsk*2; a.k_nb2 = (size_t) a.n_kv*a.hsk*2; a.k_nb3 = a.k_nb2*a.n_head_kv; a.k_type = T_F16;
     }
     if (!direct && (prefill || v->type != GGML_TYPE_F16)) {
-        p.v_bytes = (((size_t) a.hsv*a.n_kv*a.n_head_kv*2) + 255) & ~(size_t) 255;
+        p.v_bytes = (((size_t) a.hsv*a.n_kv*a.n_head_kv*2*S) + 255) & ~(size_t) 255;
         a.v = kv16 ? (char *) kv16 + p.k_bytes : nullptr; a.v_type = T_F16; a.v_trans = prefill;
-        a.v_nb1 = (size_t)(prefill ? a.n_kv : a.hsv)*2; a.v_nb2 = (size_t) a.hsv*a.n_kv*2;
+        a.v_nb1 = (size_t)(prefill ? a.n_kv : a.hsv)*2; a.v_nb2 = (size_t) a.hsv*a.n_kv*2; a.v_nb3 = a.v_nb2*a.n_head_kv;
     }
-    p.ok = attn_fa_head_sizes(a.hsk, a.hsv, (int) k->type, (int) v->type) && attn_supported(a);
+    p.ok = attn_fa_head_sizes(a.hsk, a.hsv, (int) k->type, (int) v->type) && attn_supported(a) && (size_t) a.n_head_kv*S <= 65535;      // (kv_to_f16: a grid row per (stream, kv head))
     return p;
 }
 
@@ -253,16 +256,16 @@ static void op_flash_attn_ext(mi_backend_ctx * c, struct ggml_tensor * node) {
     // what supports_op cannot see (data alignment of the views handed in) fails the graph instead of the process
     MI_REQUIRE_G(node->nb[1] == (size_t) hsv*4 && ((uintptr_t) q->data % 16) == 0);
     MI_REQUIRE_G(((uintptr_t) k->data % (k->type == GGML_TYPE_F16 || k->type == GGML_TYPE_BF16 ? 16 : 2)) == 0 && ((uintptr_t) v->data % (v->type == GGML_TYPE_F16 || v->type == GGML_TYPE_BF16 ? 16 : 2)) == 0);
-    MI_REQUIRE_G(!mask || (mask->ne[0] == n_kv && mask->ne[1] >= T && ((uintptr_t) mask->data % 16) == 0 && mask->nb[1] % 16 == 0));
+    MI_REQUIRE_G(!mask || (mask->ne[0] == n_kv && mask->ne[1] >= T && ((uintptr_t) mask->data % 16) == 0 && mask->nb[1] % 16 == 0 && mask->nb[3] % 16 == 0));
     fa_operands p = fa_kv16_plan(node, c->kv16, c->attn_part, c->attn_part_bytes);
     MI_REQUIRE_G(p.ok && p.k_bytes + p.v_bytes <= c->kv16_size);
     p.call.stream = c->stream;
     if (p.k_bytes) {
-        kv_to_f16((int) k->type, k->data, k->nb[1], k->nb[2], hd, n_kv, k->ne[2], (uint16_t *) c->kv16, /* transpose */ false, c->stream);
+        kv_to_f16((int) k->type, k->data, k->nb[1], k->nb[2], k->nb[3], hd, n_kv, k->ne[2], k->ne[3], (uint16_t *) c->kv16, /* transpose */ false, c->stream);
         c->cnt.kernels_launched++;
     }
     if (p.v_bytes) {
-        kv_to_f16((int) v->type, v->data, v->nb[1], v->nb[2], hsv, n_kv, v->ne[2], (uint16_t *) ((char *) c->kv16 + p.k_bytes), p.call.v_trans, c->stream);
+        kv_to_f16((int) v->type, v->data, v->nb[1], v->nb[2], v->nb[3], hsv, n_kv, v->ne[2], v->ne[3], (uint16_t *) ((char *) c->kv16 + p.k_bytes), p.call.v_trans, c->stream);
         c->cnt.kernels_launched++;
     }
     if (T <= 8) attn_decode(p.call); else attn_prefill(p.call);
@@ -626,34 +629,36 @@ static int try_fused_kv_store(mi_backend_ctx * c, struct ggml_cgraph * g, int i)
     return j - i + 1;
 }
 
-// MUL_MAT(k, q) -> SOFT_MAX -> MUL_MAT(v, kq) -> PERMUTE -> CONT (src/llama-graph.cpp:1283-1330)
+// MUL_MAT(k, q) -> SOFT_MAX -> MUL_MAT(v, kq) -> PERMUTE -> CONT (src/llama-graph.cpp:1283-1330). With per-sequence KV streams every tensor of the chain has
+// ne[3] = n_stream (q [hd, T, n_head, n_stream], :1231-1238; the mask [n_kv, T_pad, 1, n_stream]) and the CONT's rows are stream-major: token t of stream s is
+// row s*T + t. One launch either way; a chain in which only some of the tensors carry streams is left to the single nodes.
 static int try_fused_attn(mi_backend_ctx * c, struct ggml_cgraph * g, int i) {
     struct ggml_tensor * kq = g->nodes[i];
     const struct ggml_tensor * k = kq->src[0]; const struct ggml_tensor * q = kq->src[1];
     const bool kq8 = k->type == GGML_TYPE_Q8_0;       // -ctk q8_0: the decode kernel reads the blocks itself (<= 8 tokens); prompts keep the generic ops
-    if ((k->type != GGML_TYPE_F16 && !kq8) || q->type != GGML_TYPE_F32 || k->ne[3] != 1 || q->ne[3] != 1) return 0;
-    const int64_t hd = k->ne[0], n_kv = k->ne[1], n_head_kv = k->ne[2], T = q->ne[1], n_head = q->ne[2];
+    if ((k->type != GGML_TYPE_F16 && !kq8) || q->type != GGML_TYPE_F32 || k->ne[3] != q->ne[3]) return 0;
+    const int64_t hd = k->ne[0], n_kv = k->ne[1], n_head_kv = k->ne[2], T = q->ne[1], n_head = q->ne[2], S = q->ne[3];
     const bool prefill = T > 8;      // many tokens: the matrix-core kernel with online softmax (attn_prefill.hip)
-    if (kq8 && (k->nb[0] != 34 || k->nb[2] != (size_t) hd/32*34 || k->nb[1] % 2 || (uintptr_t) k->data % 2)) return 0;
-    if ((!kq8 && (k->nb[0] != 2 || k->nb[1] % 16 || k->nb[2] % 16 || (uintptr_t) k->data % 16)) || q->nb[0] != 4 || q->nb[1] % 16 || q->nb[2] % 16 || (uintptr_t) q->data % 16) return 0;
+    if (kq8 && (k->nb[0] != 34 || k->nb[2] != (size_t) hd/32*34 || k->nb[1] % 2 || k->nb[3] % 2 || (uintptr_t) k->data % 2)) return 0;
+    if ((!kq8 && (k->nb[0] != 2 || k->nb[1] % 16 || k->nb[2] % 16 || k->nb[3] % 16 || (uintptr_t) k->data % 16)) || q->nb[0] != 4 || q->nb[1] % 16 || q->nb[2] % 16 || q->nb[3] % 16 || (uintptr_t) q->data % 16) return 0;
     const int j1 = next_real(g, i); if (j1 < 0) return 0;
     struct ggml_tensor * sm = g->nodes[j1];
     if (sm->op != GGML_OP_SOFT_MAX || sm->src[0] != kq || op_f32(sm, 1) != 0.0f || !is_internal(c, kq)) return 0;
     const struct ggml_tensor * mask = sm->src[1];
-    if (mask && (mask->ne[0] != n_kv || mask->ne[2] != 1 || mask->ne[3] != 1 || !(mask->type == GGML_TYPE_F32 || mask->type == GGML_TYPE_F16))) return 0;
+    if (mask && (mask->ne[0] != n_kv || mask->ne[2] != 1 || (mask->ne[3] != 1 && mask->ne[3] != S) || mask->nb[3] % 4 || !(mask->type == GGML_TYPE_F32 || mask->type == GGML_TYPE_F16))) return 0;
     const int j2 = next_real(g, j1); if (j2 < 0) return 0;
     struct ggml_tensor * kqv = g->nodes[j2];
     if (kqv->op != GGML_OP_MUL_MAT || kqv->src[1] != sm || !is_internal(c, sm)) return 0;
     const struct ggml_tensor * v = kqv->src[0];
-    if (v->type != GGML_TYPE_F16 || v->nb[0] != 2 || v->ne[0] != n_kv || v->ne[1] != hd || v->ne[2] != n_head_kv || v->ne[3] != 1) return 0;
+    if (v->type != GGML_TYPE_F16 || v->nb[0] != 2 || v->ne[0] != n_kv || v->ne[1] != hd || v->ne[2] != n_head_kv || v->ne[3] != S || v->nb[3] % 16) return 0;
     // PERMUTE(0,2,1,3) view then CONT into [hd*n_head, T]
     const int j3 = next_real(g, j2); if (j3 < 0) return 0;
     struct ggml_tensor * ct = g->nodes[j3];
     if (ct->op != GGML_OP_CONT || !is_internal(c, kqv)) return 0;
     const struct ggml_tensor * pm = ct->src[0];
     if (pm->op != GGML_OP_PERMUTE || pm->src[0] != kqv || !is_internal(c, pm)) return 0;
-    if (pm->ne[0] != hd || pm->ne[1] != n_head || pm->ne[2] != T || pm->ne[3] != 1) return 0;
-    if (ct->type != GGML_TYPE_F32 || !ggml_is_contiguous(ct) || ggml_nelements(ct) != hd*n_head*T) return 0;
+    if (pm->ne[0] != hd || pm->ne[1] != n_head || pm->ne[2] != T || pm->ne[3] != S) return 0;
+    if (ct->type != GGML_TYPE_F32 || !ggml_is_contiguous(ct) || ggml_nelements(ct) != hd*n_head*T*S) return 0;
     attn_call a = {};
     a.hsk = a.hsv = hd; a.n_kv = n_kv; a.n_head = n_head; a.n_head_kv = n_head_kv; a.T = T;
     a.q = q->data; a.q_nb1 = q->nb[1]; a.q_nb2 = q->nb[2]; a.q_type = (int) q->type;
@@ -662,16 +667,17 @@ static int try_fused_attn(mi_backend_ctx * c, struct ggml_cgraph * g, int i) {
     if (mask) { a.mask = mask->data; a.m_nb1 = mask->nb[1]; a.mask_type = (int) mask->type; }
     a.sinks = sm->src[2] ? (const float *) sm->src[2]->data : nullptr; a.dst = (float *) ct->data; a.dst_nb1 = (size_t) hd*n_head*4;
     a.scale = op_f32(sm, 0); a.part = c->attn_part; a.part_bytes = c->attn_part_bytes; a.stream = c->stream;
+    a.n_stream = S; a.q_nb3 = q->nb[3]; a.k_nb3 = k->nb[3]; a.v_nb3 = v->nb[3]; a.m_nb3 = mask && mask->ne[3] > 1 ? mask->nb[3] : 0; a.dst_nb3 = (size_t) T*a.dst_nb1;
     // the chain is taken at head sizes 64 / 128 only, as it always was (the prefill kernel's transposed-V form has FLASH_ATTN_EXT's other sizes too); prompts over a Q8_0 K cache keep the generic ops
     if ((hd != 64 && hd != 128) || !attn_supported(a)) return 0;
     if (prefill) {
-        if (mask && (mask->ne[1] < T || ((uintptr_t) mask->data % 16) || mask->nb[1] % 16)) return 0;
+        if (mask && (mask->ne[1] < T || ((uintptr_t) mask->data % 16) || mask->nb[1] % 16 || mask->nb[3] % 16)) return 0;
         if (v->nb[1] % 8 || v->nb[2] % 8 || ((uintptr_t) v->data % 8)) return 0;
         // wo reads the result next: hand it the bf16 copy directly (nothing reads the scratch's offset 0 during this kernel)
         const struct ggml_tensor * wo = prefill_mm_consumer(c, g, j3, ct);
-        if (wo && mul_mat_q_scratch_bytes(hd*n_head, T, wo->src[0]->ne[1]) <= c->scratch_size) { a.y16 = (uint16_t *) c->scratch; a.dst = nullptr; }
+        if (wo && mul_mat_q_scratch_bytes(hd*n_head, T*S, wo->src[0]->ne[1]) <= c->scratch_size) { a.y16 = (uint16_t *) c->scratch; a.dst = nullptr; }
         attn_prefill(a);
-        if (a.y16) c->pass.produced_bf16(i, j3, ct->data, hd*n_head, T, ct->nb[1], 0);
+        if (a.y16) c->pass.produced_bf16(i, j3, ct->data, hd*n_head, T*S, ct->nb[1], 0);
     } else attn_decode(a);
     c->cnt.kernels_launched++;
     return j3 - i + 1;

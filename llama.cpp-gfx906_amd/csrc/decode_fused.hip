@@ -168,7 +168,22 @@ struct attn_args {
     // FLASH_ATTN_EXT's other two parameters (ggml/src/ggml-cpu/ops.cpp ggml_compute_forward_flash_attn_ext_f16): logit_softcap != 0: the scaled score
     // (scale already divided by it on the host) goes through softcap * tanh(.); max_bias > 0: ALiBi — head h's mask values are multiplied by its slope
     float softcap, max_bias, m0, m1; int n_head_log2;
+    // per-sequence KV streams (kernels.h: attn_call): blockIdx.y = stream*T + token; the byte strides of q, K, V, the mask (0: shared) and the result along the
+    // stream dimension; part_ns: floats of the partial buffer per stream (T*n_head*nsplit slots). n_stream <= 1: none of these is read.
+    int n_stream; size_t q_nb3, k_nb3, v_nb3, m_nb3, dst_nb3, part_ns;
 };
+// the call as the workgroups of one stream see it: pointers moved to the stream of row `ty` of the grid, t = the token within it
+static __device__ __forceinline__ attn_args attn_stream_args(attn_args p, int ty, int & t) {
+    t = ty;
+    if (p.n_stream > 1) {
+        const int s = ty/p.T; t = ty - s*p.T;
+        p.q += (size_t) s*p.q_nb3; p.k += (size_t) s*p.k_nb3; p.v += (size_t) s*p.v_nb3;
+        if (p.mask) p.mask += (size_t) s*p.m_nb3;
+        p.dst = (float *) ((char *) p.dst + (size_t) s*p.dst_nb3);
+        if (p.part) p.part += (size_t) s*p.part_ns;
+    }
+    return p;
+}
 static __device__ __forceinline__ float attn_slope(float max_bias, float m0, float m1, int n_head_log2, int h) {
     return max_bias > 0.0f ? (h < n_head_log2 ? powf(m0, (float)(h + 1)) : powf(m1, (float)(2*(h - n_head_log2) + 1))) : 1.0f;
 }
@@ -185,9 +200,9 @@ static __device__ __forceinline__ float dot8_f16_f32(const int4v kv, const float
 
 // flash attention pads the cache view to 256 cells; everything behind the last unmasked cell is dead weight for K, the soft_max and V: find that cell
 // first (one mask value per thread and trip) and walk only up to it (a multiple of 8 cells, at least 8)
-static __device__ __forceinline__ int attn_live_cells(const attn_args & p, int kv_n) {
+static __device__ __forceinline__ int attn_live_cells(const attn_args & p, int t, int kv_n) {
     __shared__ int live_w[4];
-    const char * mr = p.mask + (size_t) blockIdx.y*p.m_nb1;
+    const char * mr = p.mask + (size_t) t*p.m_nb1;
     int last = -1;
     for (int j = threadIdx.x; j < kv_n; j += 256) {
         const float mv = p.mask_f16 ? f16_bits_to_f32(*(const uint16_t *) (mr + (size_t) j*2)) : *(const float *) (mr + (size_t) j*4);
@@ -211,7 +226,7 @@ static __device__ __forceinline__ int attn_live_cells(const attn_args & p, int k
 // HD / HDV: the sizes of a K and a V row. The row-major-V form takes every pair of attn_fa_head_sizes; a K row is KCH 16-byte chunks that LPC lanes walk
 // in KR rounds (80 and 96: the lanes past the row's end multiply a clamped chunk by a zero q), a V row DCH chunks with 256 / DCH cells side by side.
 template <int HD, bool VT = true, int KT = T_F16, int VY = T_F16, int HDV = HD>
-__global__ void __launch_bounds__(256) k_attn_decode(const attn_args p) {
+__global__ void __launch_bounds__(256) k_attn_decode(const attn_args pa) {
     constexpr bool KQ = KT == T_Q8_0;
     static_assert(!VT || ((KT == T_F16 || KT == T_Q8_0) && VY == T_F16), "transposed V: f16 V, f16 or Q8_0 K");
     static_assert(!VT || (HDV == HD && (HD == 64 || HD == 128)), "transposed V: head size 64 / 128");
@@ -219,7 +234,9 @@ __global__ void __launch_bounds__(256) k_attn_decode(const attn_args p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float * s = (float *) smem;                          // [n_kv] scores -> probabilities
     __shared__ float sh[4];
-    const int h = blockIdx.x, t = blockIdx.y;
+    int t;
+    const attn_args p = attn_stream_args(pa, blockIdx.y, t);
+    const int h = blockIdx.x;
     const int hk = h/(p.n_head/p.n_head_kv);
     const bool split = p.nsplit > 1;
     const int kv_lo = split ? (int) blockIdx.z*p.kv_chunk : 0;
@@ -247,7 +264,7 @@ __global__ void __launch_bounds__(256) k_attn_decode(const attn_args p) {
         // q: written by the launch before on other XCDs, i.e. the longest wait of this launch — asked for before anything else (the live scan below waits for the mask)
         const float * qp = (const float *) (p.q + (size_t) t*p.q_nb1 + (size_t) h*p.q_nb2) + sub*8;
         const float4v q0_ld = *(const float4v *) qp, q1_ld = *(const float4v *) (qp + 4);
-        if (!VT && !split && p.live_scan && p.mask) kv_n = attn_live_cells(p, kv_n);
+        if (!VT && !split && p.live_scan && p.mask) kv_n = attn_live_cells(p, t, kv_n);
 
         // ---- scores: s[j] = scale * K[j].q + mask[j] ----
         const char * kbase = p.k + (size_t) hk*p.k_nb2 + (KT == T_F16 ? sub*16 : KQ ? (sub >> 2)*34 : 0) + (size_t) kv_lo*p.k_nb1;
@@ -328,7 +345,7 @@ __global__ void __launch_bounds__(256) k_attn_decode(const attn_args p) {
             q0_ld[r] = *(const float4v *) qp; q1_ld[r] = *(const float4v *) (qp + 4);
             if (!KFULL && sub + r*LPC >= KCH) { q0_ld[r] = float4v{ 0.0f, 0.0f, 0.0f, 0.0f }; q1_ld[r] = q0_ld[r]; }
         }
-        if (!split && p.live_scan && p.mask) kv_n = attn_live_cells(p, kv_n);
+        if (!split && p.live_scan && p.mask) kv_n = attn_live_cells(p, t, kv_n);
 
         const char * kbase = p.k + (size_t) hk*p.k_nb2 + (KT == T_F16 ? kc[0]*16 : KQ ? (kc[0] >> 2)*34 : 0) + (size_t) kv_lo*p.k_nb1;      // the lane's first chunk
         const char * krow = p.k + (size_t) hk*p.k_nb2 + (size_t) kv_lo*p.k_nb1;                                                               // the row (further chunks)
@@ -482,8 +499,10 @@ __global__ void __launch_bounds__(256) k_attn_decode(const attn_args p) {
 
 // combine the cell ranges of one (token, head): out = sum_i w_i o_i / (sum_i w_i [+ e^(sink - M)]), w_i = l_i e^(m_i - M), M = max(m_i [, sink])
 template <int HD>      // V's head size
-__global__ void __launch_bounds__(HD) k_attn_merge(const attn_args p) {
-    const int h = blockIdx.x, t = blockIdx.y, d = threadIdx.x;
+__global__ void __launch_bounds__(HD) k_attn_merge(const attn_args pa) {
+    int t;
+    const attn_args p = attn_stream_args(pa, blockIdx.y, t);
+    const int h = blockIdx.x, d = threadIdx.x;
     const float * pr = p.part + (size_t)(t*p.n_head + h)*p.nsplit*(HD + 2);
     float M = p.sinks ? p.sinks[h] : -INFINITY;
     for (int i = 0; i < p.nsplit; i++) M = fmaxf(M, pr[(size_t) i*(HD + 2) + HD]);
@@ -505,7 +524,7 @@ static int64_t attn_split_min(bool v_trans) {
 attn_decode_plan attn_plan_decode(const attn_call & c) {
     static const bool split_on = env_on("GGML_MI355X_ATTN_SPLIT"), live_on = env_on("GGML_MI355X_ATTN_LIVE_SCAN");
     attn_decode_plan pl = {}; pl.nsplit = 1;
-    const bool kernel = c.q_type == T_F32 && c.n_head_kv > 0 && c.n_head % c.n_head_kv == 0 &&
+    const bool kernel = c.q_type == T_F32 && c.T > 0 && c.n_head > 0 && c.n_head_kv > 0 && c.n_head % c.n_head_kv == 0 && c.T*attn_n_stream(c) <= 65535 &&      // (grid.y = stream*T + token)
         (c.v_trans ? (c.k_type == T_F16 || c.k_type == T_Q8_0) && c.v_type == T_F16 && c.hsv == c.hsk && (c.hsk == 64 || c.hsk == 128)
                    : attn_decode_kv_types_fused(c.k_type, c.v_type) && attn_fa_head_sizes(c.hsk, c.hsv, c.k_type, c.v_type));
     if (!kernel) return pl;
@@ -515,8 +534,17 @@ attn_decode_plan attn_plan_decode(const attn_call & c) {
     //  - the split itself starts at attn_split_min(v_trans).
     //  - a shape that works ONLY split (its score row is beyond one LDS) is accepted from attn_split_min(true) on, for row-major V too. As a difference this is
     //    unreachable: such a shape has more than 12288 cells, above both defaults, and a set GGML_MI355X_ATTN_SPLIT_MIN gives both layouts the same value.
-    const int64_t n_kv = c.n_kv, ns = (n_kv + 127)/128 < 32 ? (n_kv + 127)/128 : 32;       // ranges of >= 128 cells, at most 32
-    if (n_kv >= attn_split_min(false) && n_kv % 32 == 0) pl.part_bytes_needed = (size_t) c.T*c.n_head*ns*(c.hsv + 2)*4;
+    const int64_t n_kv = c.n_kv;
+    int64_t ns = (n_kv + 127)/128 < 32 ? (n_kv + 127)/128 : 32;       // ranges of >= 128 cells, at most 32
+    // a slot per (stream, token, head, range). Several streams whose ranges outgrow the buffer: as many ranges as it holds, as long as that is a split (2 or
+    // more) whose ranges fit the LDS like a whole row does; else part_bytes_needed stays what the full split wants and does not fit. One stream: today's call —
+    // all ranges or none
+    const size_t per_range = (size_t) c.T*attn_n_stream(c)*c.n_head*(c.hsv + 2)*4;
+    if (n_kv >= attn_split_min(false) && n_kv % 32 == 0) {
+        const int64_t held = (int64_t)(c.part_bytes/per_range);
+        if (c.n_stream > 1 && held < ns && held >= 2 && ((n_kv + held - 1)/held + 31)/32*32*4 <= 48*1024) ns = held;
+        pl.part_bytes_needed = per_range*ns;
+    }
     const bool part_fits = pl.part_bytes_needed <= c.part_bytes;
     // without a partial buffer the whole row of scores must fit the workgroup's LDS
     pl.ok = (n_kv % 8 == 0 && n_kv*4 <= 48*1024) || (n_kv >= attn_split_min(true) && n_kv % 32 == 0 && part_fits);
@@ -549,7 +577,12 @@ void attn_decode(const attn_call & c) {
     a.n_kv = (int) c.n_kv; a.n_head = (int) c.n_head; a.n_head_kv = (int) c.n_head_kv; a.T = (int) c.T;
     attn_set_softmax(a, c);
     a.kv_chunk = pl.kv_chunk; a.nsplit = pl.nsplit; a.part = pl.nsplit > 1 ? c.part : nullptr; a.live_scan = pl.live_scan;
-    const dim3 grid((unsigned) c.n_head, (unsigned) c.T, (unsigned) pl.nsplit);
+    const int64_t S = attn_n_stream(c);
+    if (S > 1) {
+        a.n_stream = (int) S; a.q_nb3 = c.q_nb3; a.k_nb3 = c.k_nb3; a.v_nb3 = c.v_nb3; a.m_nb3 = c.m_nb3; a.dst_nb3 = c.dst_nb3;
+        a.part_ns = (size_t) c.T*c.n_head*pl.nsplit*(c.hsv + 2);
+    }
+    const dim3 grid((unsigned) c.n_head, (unsigned)(c.T*S), (unsigned) pl.nsplit);
     attn_dispatch_sizes(c.hsk, c.hsv, [&](auto hk, auto hv) {
         constexpr int HK = decltype(hk)::value, HV = decltype(hv)::value;
         if (!c.v_trans) attn_dispatch_types(c.k_type, c.v_type, [&](auto kt, auto vt) {
@@ -560,7 +593,7 @@ void attn_decode(const attn_call & c) {
             if (c.k_type == T_Q8_0) hipLaunchKernelGGL((k_attn_decode<HK, true, T_Q8_0>), grid, dim3(256), pl.lds_bytes, c.stream, a);
             else                    hipLaunchKernelGGL((k_attn_decode<HK>), grid, dim3(256), pl.lds_bytes, c.stream, a);
         }
-        if (pl.nsplit > 1) hipLaunchKernelGGL((k_attn_merge<HV>), dim3((unsigned) c.n_head, (unsigned) c.T), dim3(HV), 0, c.stream, a);
+        if (pl.nsplit > 1) hipLaunchKernelGGL((k_attn_merge<HV>), dim3((unsigned) c.n_head, (unsigned)(c.T*S)), dim3(HV), 0, c.stream, a);
     });
 }
 

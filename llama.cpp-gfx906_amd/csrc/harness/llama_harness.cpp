@@ -161,7 +161,7 @@ struct layer {
     // gpt-oss only (src/llama-model.cpp:5436-5462): projection biases, attention sinks, router and expert biases
     ggml_tensor * bq = nullptr, * bk = nullptr, * bv = nullptr, * bo = nullptr, * sinks = nullptr;
     ggml_tensor * gate_inp_b = nullptr, * gate_b = nullptr, * up_b = nullptr, * down_b = nullptr;
-    std::vector<ggml_tensor *> k_cache, v_cache;   // one per sequence stream
+    ggml_tensor * k_cache = nullptr, * v_cache = nullptr;   // [n_embd_gqa, kv_size, n_stream]: a stream per sequence (src/llama-kv-cache-unified.cpp:131-132)
     bool swa = false;                              // attends through the window cache (its k_cache / v_cache have swa_size cells)
 };
 
@@ -193,6 +193,7 @@ struct mi_llama {
     std::vector<layer> layers;
     ggml_tensor * output_norm = nullptr, * output = nullptr, * rope_freqs = nullptr;
     std::map<std::tuple<int, int, int, int>, graph_inst> graphs;   // (seq, n_tokens, n_kv, n_kv of the window cache) -> graph: the reuse of src/llama-context.cpp:728
+                                                                   // (seq = -1: the ubatch of all sequences, n_tokens each — mi_llama_decode_batch)
     int swa_size = 0;                                   // cells of the window cache (0: the model has none)
     std::vector<std::vector<int>> swa_cell_pos;         // [seq][cell] position held by a cell of the window cache, -1 = empty
     int64_t tick = 0;
@@ -329,9 +330,14 @@ ggml_tensor * build_moe_ffn(ggml_context * ctx0, ggml_cgraph * gf, const mi_llam
     return moe_out;
 }
 
-// llm_build_llama for n_tokens tokens attending to n_kv cache cells
-graph_inst build_graph(mi_llama * m, int seq, int n_tokens, int n_kv, int n_kv_swa) {
+// llm_build_llama for n_tokens tokens of sequence `seq` attending to n_kv cells of its cache stream; seq < 0: a ubatch of n_tokens tokens for EACH of the
+// n_seq_max sequences (split_equal, src/llama-kv-cache-unified.cpp:497), token t of stream s at row s*n_tokens + t, every stream attending to its own cells:
+// q, K, V and the mask carry the streams in ne[3] (src/llama-graph.cpp:1224-1270, :1421) and every token's logits are returned
+graph_inst build_graph(mi_llama * m, int seq, int n_tokens_seq, int n_kv, int n_kv_swa) {
     const mi_llama_hparams & hp = m->hp;
+    const bool batch = seq < 0;
+    const int64_t n_stream = batch ? (int64_t) m->n_past.size() : 1;
+    const int64_t n_tokens = n_tokens_seq*n_stream;
     graph_inst g;
     g.ctx = ggml_init({ 0, NULL, true });
     ggml_context * ctx0 = g.ctx;
@@ -346,7 +352,7 @@ graph_inst build_graph(mi_llama * m, int seq, int n_tokens, int n_kv, int n_kv_s
     // the backend receives its F32 result. On a layer-split rank > 0 this is the activation handed over by the previous rank.
     g.inp_embd = ggml_new_tensor_2d(ctx0, GGML_TYPE_F32, n_embd, n_tokens); ggml_set_input(g.inp_embd); ggml_set_name(g.inp_embd, "inp_embd");
     g.inp_pos  = ggml_new_tensor_1d(ctx0, GGML_TYPE_I32, n_tokens);         ggml_set_input(g.inp_pos);  ggml_set_name(g.inp_pos, "inp_pos");
-    g.kq_mask  = ggml_new_tensor_2d(ctx0, GGML_TYPE_F32, n_kv, GGML_PAD(n_tokens, GGML_KQ_MASK_PAD)); ggml_set_input(g.kq_mask);   // src/llama-graph.cpp:1421
+    g.kq_mask  = ggml_new_tensor_4d(ctx0, GGML_TYPE_F32, n_kv, GGML_PAD(n_tokens_seq, GGML_KQ_MASK_PAD), 1, n_stream); ggml_set_input(g.kq_mask);   // src/llama-graph.cpp:1421
     g.k_idxs   = ggml_new_tensor_1d(ctx0, GGML_TYPE_I64, n_tokens);                 ggml_set_input(g.k_idxs);   // :1195
     g.v_idxs   = ggml_new_tensor_1d(ctx0, GGML_TYPE_I64, hp.flash_attn ? n_tokens : n_tokens*n_embd_v_gqa); ggml_set_input(g.v_idxs);   // :1208 (v_trans: per element)
     // with flash attention the mask is cast to F16 once per graph (src/llama-graph.cpp:1423)
@@ -355,13 +361,13 @@ graph_inst build_graph(mi_llama * m, int seq, int n_tokens, int n_kv, int n_kv_s
     auto kv_dep = [&](ggml_tensor * t, int dim, bool swa, bool contig) { if (t) g.kv_deps.push_back({ t, dim, swa, contig }); };
     kv_dep(g.kq_mask, 0, false, true); kv_dep(kq_mask_f16, 0, false, true);
     if (m->swa_size > 0) {     // build_attn_inp_kv_unified_iswa (src/llama-graph.cpp:1568-1612): a second set of inputs for the window cache
-        g.kq_mask_swa = ggml_new_tensor_2d(ctx0, GGML_TYPE_F32, n_kv_swa, GGML_PAD(n_tokens, GGML_KQ_MASK_PAD)); ggml_set_input(g.kq_mask_swa);
+        g.kq_mask_swa = ggml_new_tensor_4d(ctx0, GGML_TYPE_F32, n_kv_swa, GGML_PAD(n_tokens_seq, GGML_KQ_MASK_PAD), 1, n_stream); ggml_set_input(g.kq_mask_swa);
         g.k_idxs_swa  = ggml_new_tensor_1d(ctx0, GGML_TYPE_I64, n_tokens);                                         ggml_set_input(g.k_idxs_swa);
         g.v_idxs_swa  = ggml_new_tensor_1d(ctx0, GGML_TYPE_I64, hp.flash_attn ? n_tokens : n_tokens*n_embd_v_gqa); ggml_set_input(g.v_idxs_swa);
         if (hp.flash_attn) kq_mask_swa_f16 = ggml_cast(ctx0, g.kq_mask_swa, GGML_TYPE_F16);
         kv_dep(g.kq_mask_swa, 0, true, true); kv_dep(kq_mask_swa_f16, 0, true, true);
     }
-    const int n_outputs = 1;                                                       // llama_batch_get_one: logits for the last token only
+    const int n_outputs = batch ? (int) n_tokens : 1;                              // llama_batch_get_one: logits for the last token only; the ubatch of all sequences: for every token
     g.out_ids  = ggml_new_tensor_1d(ctx0, GGML_TYPE_I32, n_outputs);                ggml_set_input(g.out_ids);
 
     ggml_tensor * inpL = g.inp_embd;
@@ -386,6 +392,10 @@ graph_inst build_graph(mi_llama * m, int seq, int n_tokens, int n_kv, int n_kv_s
         const int64_t n_kv_l = L.swa ? n_kv_swa : n_kv;
         ggml_tensor * l_mask = L.swa ? g.kq_mask_swa : g.kq_mask, * l_mask_f16 = L.swa ? kq_mask_swa_f16 : kq_mask_f16;
         ggml_tensor * l_k_idxs = L.swa ? g.k_idxs_swa : g.k_idxs, * l_v_idxs = L.swa ? g.v_idxs_swa : g.v_idxs;
+        // the cache as this graph writes and reads it: one sequence sees its stream (a 2-D view), the ubatch of all sequences every stream: SET_ROWS into the 2-D view
+        // [n_embd_gqa, kv_size*n_stream] with indices offset by s*kv_size (cpy_k / cpy_v, src/llama-kv-cache-unified.cpp:1108-1190), K / V as 4-D views (get_k / get_v)
+        ggml_tensor * kc = batch ? ggml_reshape_2d(ctx0, L.k_cache, n_embd_k_gqa, kv_size*n_stream) : ggml_view_2d(ctx0, L.k_cache, n_embd_k_gqa, kv_size, L.k_cache->nb[1], seq*L.k_cache->nb[2]);
+        ggml_tensor * vc = batch ? ggml_reshape_2d(ctx0, L.v_cache, n_embd_v_gqa, kv_size*n_stream) : ggml_view_2d(ctx0, L.v_cache, n_embd_v_gqa, kv_size, L.v_cache->nb[1], seq*L.v_cache->nb[2]);
 
         // build_norm(inpL, attn_norm, NULL, LLM_NORM_RMS)
         cur = ggml_rms_norm(ctx0, inpL, hp.f_norm_rms_eps);
@@ -413,29 +423,29 @@ graph_inst build_graph(mi_llama * m, int seq, int n_tokens, int n_kv, int n_kv_s
         ggml_build_forward_expand(g.gf, Vcur);
         {   // store to KV cache: cpy_k / cpy_v with set_rows (src/llama-kv-cache-unified.cpp:1108-1190)
             ggml_tensor * k_cur2 = ggml_reshape_2d(ctx0, Kcur, n_embd_k_gqa, n_tokens);
-            ggml_build_forward_expand(g.gf, ggml_set_rows(ctx0, L.k_cache[seq], k_cur2, l_k_idxs));
+            ggml_build_forward_expand(g.gf, ggml_set_rows(ctx0, kc, k_cur2, l_k_idxs));
             ggml_tensor * v_cur2 = ggml_reshape_2d(ctx0, Vcur, n_embd_v_gqa, n_tokens);
             if (hp.flash_attn) {      // !v_trans: a row scatter like K (:1154)
-                ggml_build_forward_expand(g.gf, ggml_set_rows(ctx0, L.v_cache[seq], v_cur2, l_v_idxs));
+                ggml_build_forward_expand(g.gf, ggml_set_rows(ctx0, vc, v_cur2, l_v_idxs));
             } else {
-                ggml_tensor * v_view = ggml_reshape_2d(ctx0, L.v_cache[seq], 1, n_embd_v_gqa*kv_size);     // the row becomes a single element
+                ggml_tensor * v_view = ggml_reshape_2d(ctx0, vc, 1, n_embd_v_gqa*kv_size*n_stream);     // the row becomes a single element
                 v_cur2 = ggml_reshape_2d(ctx0, v_cur2, 1, n_embd_v_gqa*n_tokens);
                 ggml_build_forward_expand(g.gf, ggml_set_rows(ctx0, v_view, v_cur2, l_v_idxs));
             }
         }
         // get_k / get_v (:1056-1106), v_trans layout
-        const enum ggml_type tk = L.k_cache[seq]->type;
-        ggml_tensor * k = ggml_view_4d(ctx0, L.k_cache[seq], hd, n_head_kv, n_kv_l, 1,
+        const enum ggml_type tk = L.k_cache->type;
+        ggml_tensor * k = ggml_view_4d(ctx0, kc, hd, n_head_kv, n_kv_l, n_stream,
                 ggml_row_size(tk, hd), ggml_row_size(tk, n_embd_k_gqa), ggml_row_size(tk, n_embd_k_gqa*kv_size), 0);
-        const enum ggml_type tv = L.v_cache[seq]->type;
+        const enum ggml_type tv = L.v_cache->type;
         ggml_tensor * v = hp.flash_attn
-            ? ggml_view_4d(ctx0, L.v_cache[seq], hd, n_head_kv, n_kv_l, 1,      // !v_trans (:1087-1096)
+            ? ggml_view_4d(ctx0, vc, hd, n_head_kv, n_kv_l, n_stream,      // !v_trans (:1087-1096)
                 ggml_row_size(tv, hd), ggml_row_size(tv, n_embd_v_gqa), ggml_row_size(tv, n_embd_v_gqa*kv_size), 0)
-            : ggml_view_4d(ctx0, L.v_cache[seq], n_kv_l, n_head_kv, hd, 1,
+            : ggml_view_4d(ctx0, vc, n_kv_l, n_head_kv, hd, n_stream,
                 ggml_row_size(GGML_TYPE_F16, kv_size*hd), ggml_row_size(GGML_TYPE_F16, kv_size), ggml_row_size(GGML_TYPE_F16, kv_size*n_embd_v_gqa), 0);
         kv_dep(k, 2, L.swa, false); kv_dep(v, hp.flash_attn ? 2 : 0, L.swa, false);
         if (hp.flash_attn) {   // build_attn_mha with flash attention (src/llama-graph.cpp:1245-1265, :1337): n_kv % 256 == 0 by the cache's padding
-            ggml_tensor * q = ggml_reshape_4d(ctx0, Qcur, Qcur->ne[0], Qcur->ne[1], Qcur->ne[2], 1);
+            ggml_tensor * q = ggml_reshape_4d(ctx0, Qcur, Qcur->ne[0], Qcur->ne[1], Qcur->ne[2]/n_stream, n_stream);
             q = ggml_permute(ctx0, q, 0, 2, 1, 3);
             k = ggml_permute(ctx0, k, 0, 2, 1, 3);
             v = ggml_permute(ctx0, v, 0, 2, 1, 3);
@@ -446,7 +456,7 @@ graph_inst build_graph(mi_llama * m, int seq, int n_tokens, int n_kv, int n_kv_s
             cur = ggml_reshape_2d(ctx0, cur, cur->ne[0]*cur->ne[1], cur->ne[2]*cur->ne[3]);
             ggml_build_forward_expand(g.gf, cur);
         } else {   // build_attn_mha, no flash attention (src/llama-graph.cpp:1283-1341)
-            ggml_tensor * q = ggml_reshape_4d(ctx0, Qcur, Qcur->ne[0], Qcur->ne[1], Qcur->ne[2], 1);
+            ggml_tensor * q = ggml_reshape_4d(ctx0, Qcur, Qcur->ne[0], Qcur->ne[1], Qcur->ne[2]/n_stream, n_stream);
             q = ggml_permute(ctx0, q, 0, 2, 1, 3);
             k = ggml_permute(ctx0, k, 0, 2, 1, 3);
             v = ggml_permute(ctx0, v, 0, 2, 1, 3);
@@ -678,10 +688,8 @@ mi_llama * create_body(mi_llama * m) {
         }
         // KV cache on the layer's device, F16 (src/llama-kv-cache-unified.cpp:114-132)
         L.swa = hp.n_swa > 0 && (hp.swa_pattern <= 0 || il % hp.swa_pattern < hp.swa_pattern - 1);     // llama_hparams::set_swa_pattern
-        for (int sq = 0; sq < std::max(1, hp.n_seq_max); sq++) {
-            L.k_cache.push_back(ggml_new_tensor_2d(m->kvctx, hp.type_k ? (enum ggml_type) hp.type_k : GGML_TYPE_F16, n_embd_k_gqa, L.swa ? m->swa_size : kv_size));
-            L.v_cache.push_back(ggml_new_tensor_2d(m->kvctx, hp.type_v ? (enum ggml_type) hp.type_v : GGML_TYPE_F16, n_embd_v_gqa, L.swa ? m->swa_size : kv_size));
-        }
+        L.k_cache = ggml_new_tensor_3d(m->kvctx, hp.type_k ? (enum ggml_type) hp.type_k : GGML_TYPE_F16, n_embd_k_gqa, L.swa ? m->swa_size : kv_size, std::max(1, hp.n_seq_max));
+        L.v_cache = ggml_new_tensor_3d(m->kvctx, hp.type_v ? (enum ggml_type) hp.type_v : GGML_TYPE_F16, n_embd_v_gqa, L.swa ? m->swa_size : kv_size, std::max(1, hp.n_seq_max));
         m->layers.push_back(L);
     }
     if (hp.has_rope_freqs) m->rope_freqs = new_weight(m, GGML_TYPE_F32, hd/2, 1, "rope_freqs.weight");
@@ -720,7 +728,8 @@ mi_llama * create_body(mi_llama * m) {
     ggml_backend_buffer_type_t hbt = ggml_backend_dev_host_buffer_type(ggml_backend_get_device(backend));
     {   // 4 slots, each large enough for the inputs of one decode of up to n_ctx tokens: embeddings, mask, K / V indices, positions
         const size_t nc = (size_t) hp.n_ctx;
-        const size_t slot = nc*hp.n_embd*4 + (hp.n_swa > 0 ? 2 : 1)*(nc*GGML_PAD(nc, GGML_KQ_MASK_PAD)*4 + nc*(size_t) n_embd_v_gqa*8 + nc*16) + (64u << 10);
+        // (a ubatch of all sequences: up to n_ctx tokens in all, and a mask of PAD(n_tokens) rows per sequence)
+        const size_t slot = nc*hp.n_embd*4 + (hp.n_swa > 0 ? 2 : 1)*((nc + (size_t) std::max(1, hp.n_seq_max)*GGML_KQ_MASK_PAD)*GGML_PAD(nc, GGML_KQ_MASK_PAD)*4 + nc*(size_t) n_embd_v_gqa*8 + nc*16) + nc*4 + (64u << 10);
         m->hsize = 4*((slot + 4095) & ~(size_t) 4095);
     }
     if (hbt) {
@@ -856,32 +865,42 @@ GGML_API struct ggml_tensor * mi_llama_get_tensor(struct mi_llama * m, const cha
 //   result_host : optional host buffer for the result (n_vocab logits of the last token, or [n_embd, n_tokens] l_out on non-final ranks)
 //   dev_result_out : optional DEVICE pointer that receives the result instead (hand-off to the next rank)
 //   do_sync : bit 0 = synchronize before returning; bit 1 = no host read-back (measurements)
-GGML_API int mi_llama_decode(struct mi_llama * m, int seq, const int32_t * tokens, int n_tokens, const void * dev_act_in,
-                             float * result_host, void * dev_result_out, int do_sync) {
+// seq < 0 (mi_llama_decode_batch): one ubatch of n_tokens tokens for EACH sequence, tokens[s*n_tokens + t]; stream s of the graph is sequence s, n_kv the
+// largest stream's; the result is every token's logits, [n_seq_max*n_tokens, n_vocab]
+static int decode_ubatch(struct mi_llama * m, int seq, const int32_t * tokens, int n_tokens, const void * dev_act_in,
+                         float * result_host, void * dev_result_out, int do_sync) {
     const mi_llama_hparams & hp = m->hp;
-    if (seq < 0 || seq >= (int) m->n_past.size()) return -1;
-    if (n_tokens <= 0 || m->n_past[seq] + n_tokens > hp.n_ctx) return 1;   // "could not find a KV slot" (src/llama-context.cpp:1006)
-    const int head = m->n_past[seq];
+    const bool batch = seq < 0;
+    const int n_stream = batch ? (int) m->n_past.size() : 1, n_all = n_tokens*n_stream;
+    auto seq_of = [&](int s) { return batch ? s : seq; };      // the sequence whose cache stream is stream s of the graph
+    if (!batch && seq >= (int) m->n_past.size()) return -1;
+    if (n_tokens <= 0 || n_all > hp.n_ctx) return 1;
+    for (int s = 0; s < n_stream; s++) if (m->n_past[seq_of(s)] + n_tokens > hp.n_ctx) return 1;   // "could not find a KV slot" (src/llama-context.cpp:1006)
+    std::vector<int> heads(n_stream);
+    for (int s = 0; s < n_stream; s++) heads[s] = m->n_past[seq_of(s)];
     const int kv_pad = hp.flash_attn ? 256 : KV_PAD;                                                   // get_padding (:2407-2410)
-    const int n_kv = std::min(hp.n_ctx, std::max(kv_pad, (int) GGML_PAD(head + n_tokens, kv_pad)));   // get_n_kv (:1040-1050)
+    int n_kv = 0;                                                                                      // get_n_kv (:1040-1050): over all streams of the ubatch
+    for (int s = 0; s < n_stream; s++) n_kv = std::max(n_kv, std::min(hp.n_ctx, std::max(kv_pad, (int) GGML_PAD(heads[s] + n_tokens, kv_pad))));
 
     // the window cache: a token at position p lives in cell p % swa_size (the cell it overwrites held p - swa_size, out of every
     // window that is still open since swa_size >= n_swa + n_tokens); n_kv covers the highest cell in use (get_n_kv)
     int n_kv_swa = 0;
     if (m->swa_size > 0) {
         if (m->swa_size < hp.n_ctx && hp.n_swa + n_tokens > m->swa_size) return 1;      // a batch beyond n_ubatch would overwrite cells of its own window
-        std::vector<int> & cp = m->swa_cell_pos[seq];
-        for (int i = 0; i < n_tokens; i++) cp[(head + i) % m->swa_size] = head + i;
         int used_max_p1 = 0;
-        for (int j = 0; j < m->swa_size; j++) if (cp[j] >= 0) used_max_p1 = j + 1;
+        for (int s = 0; s < n_stream; s++) {
+            std::vector<int> & cp = m->swa_cell_pos[seq_of(s)];
+            for (int i = 0; i < n_tokens; i++) cp[(heads[s] + i) % m->swa_size] = heads[s] + i;
+            for (int j = 0; j < m->swa_size; j++) if (cp[j] >= 0) used_max_p1 = std::max(used_max_p1, j + 1);
+        }
         n_kv_swa = std::min(m->swa_size, std::max(kv_pad, (int) GGML_PAD(used_max_p1, kv_pad)));
     }
     // MI_HARNESS_REUSE_GRAPH=1 (tests): llama.cpp rebuilds a graph in the same buf_compute_meta and lets ggml-alloc place it in the same compute buffer, so
     // from one n_kv bucket to the next the backend sees the same node objects at the same addresses with other shapes; this harness otherwise builds a
     // graph of its own, every tensor in memory of its own, per n_kv. In this mode one graph per (seq, n_tokens) is built for n_kv = n_ctx (the window cache:
     // its size) — the worst-case reservation — and the n_kv-dependent tensors (masks, K / V views, their permutes, the K.q scores) are resized in place.
-    const bool reuse = getenv("MI_HARNESS_REUSE_GRAPH") && atoi(getenv("MI_HARNESS_REUSE_GRAPH")) != 0;
-    auto key = reuse ? std::make_tuple(seq, n_tokens, -1, -1) : std::make_tuple(seq, n_tokens, n_kv, n_kv_swa);
+    const bool reuse = !batch && getenv("MI_HARNESS_REUSE_GRAPH") && atoi(getenv("MI_HARNESS_REUSE_GRAPH")) != 0;
+    auto key = reuse ? std::make_tuple(seq, n_tokens, -1, -1) : std::make_tuple(batch ? -1 : seq, n_tokens, n_kv, n_kv_swa);
     auto it = m->graphs.find(key);
     if (it == m->graphs.end()) {
         if (m->graphs.size() >= 6*m->n_past.size()) {   // bound the number of live compute buffers
@@ -891,7 +910,7 @@ GGML_API int mi_llama_decode(struct mi_llama * m, int seq, const int32_t * token
             free_graph(victim->second);
             m->graphs.erase(victim);
         }
-        it = m->graphs.emplace(key, reuse ? build_graph(m, seq, n_tokens, hp.n_ctx, m->swa_size) : build_graph(m, seq, n_tokens, n_kv, n_kv_swa)).first;
+        it = m->graphs.emplace(key, reuse ? build_graph(m, seq, n_tokens, hp.n_ctx, m->swa_size) : build_graph(m, batch ? -1 : seq, n_tokens, n_kv, n_kv_swa)).first;
     }
     graph_inst & g = it->second;
     if (reuse) set_graph_n_kv(g, n_kv, n_kv_swa);
@@ -908,8 +927,8 @@ GGML_API int mi_llama_decode(struct mi_llama * m, int seq, const int32_t * token
         if (!m->set_from_device) return -4;
         m->set_from_device(m->backend, g.inp_embd, dev_act_in, 0, ggml_nbytes(g.inp_embd));   // device-to-device
     } else {
-        float * e = (float *) stage((size_t) n_embd*n_tokens*4);
-        if (m->tok_embd) for (int i = 0; i < n_tokens; i++) { const int32_t tk = tokens ? tokens[i] : i; if (tk < 0 || tk >= hp.n_vocab) return -1; }   // llama_decode: "invalid token" (src/llama-batch.cpp:60-75)
+        float * e = (float *) stage((size_t) n_embd*n_all*4);
+        if (m->tok_embd) for (int i = 0; i < n_all; i++) { const int32_t tk = tokens ? tokens[i] : i; if (tk < 0 || tk >= hp.n_vocab) return -1; }   // llama_decode: "invalid token" (src/llama-batch.cpp:60-75)
         // GET_ROWS(token_embd, tokens) on the host (build_inp_embd, src/llama-graph.cpp:1059-1075) — the CPU backend runs it on its thread pool, so a prompt's
         // rows are spread over threads here too (one thread generated 512 x 4096 synthetic values in 3.9 ms: a quarter of a pp512 pass spent in the test harness)
         auto rows = [&](int i0, int i1) {
@@ -919,71 +938,77 @@ GGML_API int mi_llama_decode(struct mi_llama * m, int seq, const int32_t * token
                 else synth_embedding(e + (size_t) i*n_embd, (int) n_embd, tk, m->seed);
             }
         };
-        const unsigned nthr = n_tokens >= 32 ? std::max(1u, std::min(std::min(16u, std::thread::hardware_concurrency()), (unsigned) n_tokens/8)) : 1u;
-        if (nthr <= 1) rows(0, n_tokens);
+        const unsigned nthr = n_all >= 32 ? std::max(1u, std::min(std::min(16u, std::thread::hardware_concurrency()), (unsigned) n_all/8)) : 1u;
+        if (nthr <= 1) rows(0, n_all);
         else {
             std::vector<std::thread> th;
-            for (unsigned t = 0; t < nthr; t++) th.emplace_back(rows, (int)((int64_t) n_tokens*t/nthr), (int)((int64_t) n_tokens*(t + 1)/nthr));
+            for (unsigned t = 0; t < nthr; t++) th.emplace_back(rows, (int)((int64_t) n_all*t/nthr), (int)((int64_t) n_all*(t + 1)/nthr));
             for (auto & x : th) x.join();
         }
         ggml_backend_tensor_set_async(m->backend, g.inp_embd, e, 0, ggml_nbytes(g.inp_embd));
     }
+    // (token i of stream s is row s*n_tokens + i of every per-token input; a stream's cells start s*kv_size rows into the 2-D view of the cache the ubatch of all
+    // sequences writes through — one sequence writes through the view of its own stream: no offset)
     {
-        int32_t * p = (int32_t *) stage((size_t) n_tokens*4);
-        for (int i = 0; i < n_tokens; i++) p[i] = head + i;
+        int32_t * p = (int32_t *) stage((size_t) n_all*4);
+        for (int s = 0; s < n_stream; s++) for (int i = 0; i < n_tokens; i++) p[s*n_tokens + i] = heads[s] + i;
         ggml_backend_tensor_set_async(m->backend, g.inp_pos, p, 0, ggml_nbytes(g.inp_pos));
     }
-    {   // causal mask over the used cells (set_input_kq_mask)
+    {   // causal mask over the used cells (set_input_kq_mask), [n_kv, PAD(n_tokens), 1, n_stream]
         const int64_t ne0 = g.kq_mask->ne[0], ne1 = g.kq_mask->ne[1];
-        float * p = (float *) stage((size_t) ne0*ne1*4);
-        for (int64_t i = 0; i < ne0*ne1; i++) p[i] = -INFINITY;
-        for (int i = 0; i < n_tokens; i++) {
-            const int p1 = head + i;
-            for (int j = 0; j <= p1 && j < n_kv; j++) p[(int64_t) i*ne0 + j] = 0.0f;
+        float * p = (float *) stage((size_t) ne0*ne1*n_stream*4);
+        for (int64_t i = 0; i < ne0*ne1*n_stream; i++) p[i] = -INFINITY;
+        for (int s = 0; s < n_stream; s++) for (int i = 0; i < n_tokens; i++) {
+            const int p1 = heads[s] + i;
+            for (int j = 0; j <= p1 && j < n_kv; j++) p[((int64_t) s*ne1 + i)*ne0 + j] = 0.0f;
         }
         ggml_backend_tensor_set_async(m->backend, g.kq_mask, p, 0, ggml_nbytes(g.kq_mask));
     }
     {
-        int64_t * p = (int64_t *) stage((size_t) n_tokens*8);
-        for (int i = 0; i < n_tokens; i++) p[i] = head + i;
+        int64_t * p = (int64_t *) stage((size_t) n_all*8);
+        for (int s = 0; s < n_stream; s++) for (int i = 0; i < n_tokens; i++) p[s*n_tokens + i] = (batch ? s*kv_size : 0) + heads[s] + i;
         ggml_backend_tensor_set_async(m->backend, g.k_idxs, p, 0, ggml_nbytes(g.k_idxs));
     }
     if (hp.flash_attn) {   // V rows are cells: one index per token (set_input_v_idxs :1240-1250)
-        int64_t * p = (int64_t *) stage((size_t) n_tokens*8);
-        for (int i = 0; i < n_tokens; i++) p[i] = head + i;
+        int64_t * p = (int64_t *) stage((size_t) n_all*8);
+        for (int s = 0; s < n_stream; s++) for (int i = 0; i < n_tokens; i++) p[s*n_tokens + i] = (batch ? s*kv_size : 0) + heads[s] + i;
         ggml_backend_tensor_set_async(m->backend, g.v_idxs, p, 0, ggml_nbytes(g.v_idxs));
     } else {   // v_trans: one index per element (set_input_v_idxs :1252-1267)
-        int64_t * p = (int64_t *) stage((size_t) n_tokens*n_embd_v_gqa*8);
-        for (int i = 0; i < n_tokens; i++)
-            for (int64_t j = 0; j < n_embd_v_gqa; j++) p[(int64_t) i*n_embd_v_gqa + j] = j*kv_size + head + i;
+        int64_t * p = (int64_t *) stage((size_t) n_all*n_embd_v_gqa*8);
+        for (int s = 0; s < n_stream; s++) for (int i = 0; i < n_tokens; i++)
+            for (int64_t j = 0; j < n_embd_v_gqa; j++) p[(int64_t)(s*n_tokens + i)*n_embd_v_gqa + j] = (batch ? s*kv_size*n_embd_v_gqa : 0) + j*kv_size + heads[s] + i;
         ggml_backend_tensor_set_async(m->backend, g.v_idxs, p, 0, ggml_nbytes(g.v_idxs));
     }
     if (m->swa_size > 0) {   // the same three inputs for the window cache (llm_graph_input_attn_kv_unified_iswa::set_input, src/llama-graph.cpp:353-369)
-        const std::vector<int> & cp = m->swa_cell_pos[seq];
         const int64_t ne0 = g.kq_mask_swa->ne[0], ne1 = g.kq_mask_swa->ne[1], ssz = m->swa_size;
-        float * pm = (float *) stage((size_t) ne0*ne1*4);
-        for (int64_t i = 0; i < ne0*ne1; i++) pm[i] = -INFINITY;
-        for (int i = 0; i < n_tokens; i++) {
-            const int p1 = head + i;
+        float * pm = (float *) stage((size_t) ne0*ne1*n_stream*4);
+        for (int64_t i = 0; i < ne0*ne1*n_stream; i++) pm[i] = -INFINITY;
+        for (int s = 0; s < n_stream; s++) for (int i = 0; i < n_tokens; i++) {
+            const std::vector<int> & cp = m->swa_cell_pos[seq_of(s)];
+            const int p1 = heads[s] + i;
             // is_masked_swa, LLAMA_SWA_TYPE_STANDARD (src/llama-hparams.cpp / llama-kv-cache-unified.cpp:1337-1358): empty, future, or p1 - p0 >= n_swa
-            for (int j = 0; j < n_kv_swa; j++) if (cp[j] >= 0 && cp[j] <= p1 && p1 - cp[j] < hp.n_swa) pm[(int64_t) i*ne0 + j] = 0.0f;
+            for (int j = 0; j < n_kv_swa; j++) if (cp[j] >= 0 && cp[j] <= p1 && p1 - cp[j] < hp.n_swa) pm[((int64_t) s*ne1 + i)*ne0 + j] = 0.0f;
         }
         ggml_backend_tensor_set_async(m->backend, g.kq_mask_swa, pm, 0, ggml_nbytes(g.kq_mask_swa));
-        int64_t * pk = (int64_t *) stage((size_t) n_tokens*8);
-        for (int i = 0; i < n_tokens; i++) pk[i] = (head + i) % ssz;
+        int64_t * pk = (int64_t *) stage((size_t) n_all*8);
+        for (int s = 0; s < n_stream; s++) for (int i = 0; i < n_tokens; i++) pk[s*n_tokens + i] = (batch ? s*ssz : 0) + (heads[s] + i) % ssz;
         ggml_backend_tensor_set_async(m->backend, g.k_idxs_swa, pk, 0, ggml_nbytes(g.k_idxs_swa));
         if (hp.flash_attn) {
-            int64_t * pv = (int64_t *) stage((size_t) n_tokens*8);
-            for (int i = 0; i < n_tokens; i++) pv[i] = (head + i) % ssz;
+            int64_t * pv = (int64_t *) stage((size_t) n_all*8);
+            for (int s = 0; s < n_stream; s++) for (int i = 0; i < n_tokens; i++) pv[s*n_tokens + i] = (batch ? s*ssz : 0) + (heads[s] + i) % ssz;
             ggml_backend_tensor_set_async(m->backend, g.v_idxs_swa, pv, 0, ggml_nbytes(g.v_idxs_swa));
         } else {
-            int64_t * pv = (int64_t *) stage((size_t) n_tokens*n_embd_v_gqa*8);
-            for (int i = 0; i < n_tokens; i++)
-                for (int64_t j = 0; j < n_embd_v_gqa; j++) pv[(int64_t) i*n_embd_v_gqa + j] = j*ssz + (head + i) % ssz;
+            int64_t * pv = (int64_t *) stage((size_t) n_all*n_embd_v_gqa*8);
+            for (int s = 0; s < n_stream; s++) for (int i = 0; i < n_tokens; i++)
+                for (int64_t j = 0; j < n_embd_v_gqa; j++) pv[(int64_t)(s*n_tokens + i)*n_embd_v_gqa + j] = (batch ? s*ssz*n_embd_v_gqa : 0) + j*ssz + (heads[s] + i) % ssz;
             ggml_backend_tensor_set_async(m->backend, g.v_idxs_swa, pv, 0, ggml_nbytes(g.v_idxs_swa));
         }
     }
-    {
+    if (batch) {      // every token is an output
+        int32_t * p = (int32_t *) stage((size_t) n_all*4);
+        for (int i = 0; i < n_all; i++) p[i] = i;
+        ggml_backend_tensor_set_async(m->backend, g.out_ids, p, 0, ggml_nbytes(g.out_ids));
+    } else {
         int32_t * p = (int32_t *) stage(4);
         p[0] = n_tokens - 1;
         ggml_backend_tensor_set_async(m->backend, g.out_ids, p, 0, 4);
@@ -1005,9 +1030,22 @@ GGML_API int mi_llama_decode(struct mi_llama * m, int seq, const int32_t * token
         if (!result_host) { if (!reserve_result(m, rbytes/4)) return -2; m->logits_n = rbytes/4; }
         ggml_backend_tensor_get_async(m->backend, g.result, result_host ? result_host : m->logits, 0, rbytes);
     }
-    m->n_past[seq] += n_tokens;
+    for (int s = 0; s < n_stream; s++) m->n_past[seq_of(s)] += n_tokens;
     if (do_sync & 1) ggml_backend_synchronize(m->backend);   // llama_synchronize (llama-bench.cpp:1806 does it after every token)
     return 0;
+}
+
+GGML_API int mi_llama_decode(struct mi_llama * m, int seq, const int32_t * tokens, int n_tokens, const void * dev_act_in,
+                             float * result_host, void * dev_result_out, int do_sync) {
+    if (seq < 0) return -1;
+    return decode_ubatch(m, seq, tokens, n_tokens, dev_act_in, result_host, dev_result_out, do_sync);
+}
+
+// One llama_decode() of a ubatch that holds n_tokens_per_seq tokens of EVERY sequence (kv_unified = false, equal split): tokens[s*n_tokens_per_seq + t].
+// The result, read with mi_llama_last_logits / mi_llama_n_result, is [n_seq_max*n_tokens_per_seq, n_vocab], token t of sequence s at row s*n_tokens_per_seq + t.
+// do_sync as mi_llama_decode.
+GGML_API int mi_llama_decode_batch(struct mi_llama * m, const int32_t * tokens, int n_tokens_per_seq, int do_sync) {
+    return decode_ubatch(m, -1, tokens, n_tokens_per_seq, nullptr, nullptr, nullptr, do_sync);
 }
 
 // the synthetic embedding row the harness feeds for `token` (so that tests can rebuild the same input)

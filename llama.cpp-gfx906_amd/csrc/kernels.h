@@ -233,6 +233,10 @@ struct attn_call {
     float * dst; size_t dst_nb1;                          // [hsv*n_head, T]; NULL (prefill): only y16 is wanted
     uint16_t * y16;                                       // prefill: also the bf16 copy the following mat-mul reads, rows of hsv*n_head rounded up to a multiple of 64
     int64_t hsk, hsv, n_kv, n_head, n_head_kv, T;
+    // per-sequence KV streams (kv_unified = false, src/llama-graph.cpp:1231-1238): n_stream sequences of T tokens each in one launch, every one over its own K / V
+    // (and mask); 0 or 1: one stream, the strides below are not read. Byte strides along the stream dimension (ne[3]); m_nb3 = 0: one mask for all streams.
+    // dst_nb3: stream s's rows start T rows behind stream s - 1's in a dense [hsv*n_head, T*n_stream] result. y16 rows likewise. Sinks are per head.
+    int64_t n_stream; size_t q_nb3, k_nb3, v_nb3, m_nb3, dst_nb3;
     float scale, softcap, max_bias;                       // logit_softcap and ALiBi: FLASH_ATTN_EXT's other two parameters (0: none)
     float * part; size_t part_bytes;                      // decode: the partial-result buffer on offer (0 bytes: none)
     hipStream_t stream;
@@ -240,22 +244,25 @@ struct attn_call {
 // Decode, planned once. Long contexts (a multiple of 32 cells): with the partial buffer the cells are split into nsplit ranges of kv_chunk (up to 32 workgroups per
 // (head, token)) that a second small kernel merges; live_scan: one workgroup per head that stops at the last unmasked cell. ok: there is a kernel for the
 // head sizes and types (v_trans: 64 / 128, F16 or Q8_0 K, F16 V; row-major V: attn_fa_head_sizes, attn_decode_kv_types_fused) and the score row fits the LDS
-// (n_kv % 8 == 0 up to 12288 cells) or its ranges fit part_bytes. part_bytes_needed: 0 = no split for this shape.
+// (n_kv % 8 == 0 up to 12288 cells) or its ranges fit part_bytes. part_bytes_needed: 0 = no split for this shape. The buffer holds a slot per (stream, token, head,
+// range): with several streams, when the full count of ranges does not fit, fewer are taken (at least 2, each within one LDS); when none fits and the row does not
+// either, ok = false. (One stream keeps the rule it had: the full count or no split.)
 struct attn_decode_plan { bool ok; int nsplit, kv_chunk; bool live_scan; size_t lds_bytes, part_bytes_needed; };
 attn_decode_plan attn_plan_decode(const attn_call & c);
-// Prefill: one wave per (head, 32 queries), nw waves per workgroup = hpw heads of one kv head x query tiles x ks-way split cell blocks. ok: F16 K and V, n_kv % 32 == 0,
+// Prefill: one wave per (head, 32 queries), nw waves per workgroup = hpw heads of one kv head x query tiles x ks-way split cell blocks; grid.z = the stream. ok: F16 K and V, n_kv % 32 == 0,
 // head sizes: v_trans: attn_fa_head_sizes; row-major V: 64 / 128
 struct attn_prefill_plan { bool ok; int nw, hpw, ks; dim3 grid; };
 attn_prefill_plan attn_plan_prefill(const attn_call & c);
 // the one support answer, for supports_op (part_bytes = ATTN_PART_BYTES) and the nodes themselves (the buffer they have): the plan's ok for the operands as
 // the launcher gets them — FLASH_ATTN_EXT's after fa_kv16_plan's conversions (backend_nodes.cpp)
+inline int64_t attn_n_stream(const attn_call & c) { return c.n_stream > 1 ? c.n_stream : 1; }
 inline bool attn_supported(const attn_call & c) { return c.T > 8 ? attn_plan_prefill(c).ok : attn_plan_decode(c).ok; }
 void attn_decode(const attn_call & c);       // T <= 8
 void attn_prefill(const attn_call & c);      // T > 8
-// K / V cache views [hd, n_kv, n_head_kv] of type F16 / BF16 / Q8_0 / Q4_0 -> dense f16: rows of cells [n_head_kv][n_kv][hd], or transposed
-// (rows over cells, the layout the matrix-core prefill kernel stages with coalesced loads) [n_head_kv][hd][n_kv]; n_kv % 8 == 0; hd (the size of the tensor
-// converted, K's or V's): a multiple of 8 (of 32 for Q8_0 / Q4_0) up to 256
-void kv_to_f16(int type, const void * src, size_t nb1, size_t nb2, int64_t hd, int64_t n_kv, int64_t n_head_kv, uint16_t * dst, bool transpose, hipStream_t stream);
+// K / V cache views [hd, n_kv, n_head_kv, n_stream] of type F16 / BF16 / Q8_0 / Q4_0 -> dense f16: rows of cells [n_stream][n_head_kv][n_kv][hd], or transposed
+// (rows over cells, the layout the matrix-core prefill kernel stages with coalesced loads) [n_stream][n_head_kv][hd][n_kv]; n_kv % 8 == 0; hd (the size of the tensor
+// converted, K's or V's): a multiple of 8 (of 32 for Q8_0 / Q4_0) up to 256. One launch for all streams, each stream's copy dense behind the previous one's.
+void kv_to_f16(int type, const void * src, size_t nb1, size_t nb2, size_t nb3, int64_t hd, int64_t n_kv, int64_t n_head_kv, int64_t n_stream, uint16_t * dst, bool transpose, hipStream_t stream);
 // the soft_max's constants as both kernels' argument structs carry them: the scale divided by logit_softcap, and ALiBi's slopes
 // (ggml_compute_forward_flash_attn_ext_f16 / soft_max: m0 = 2^(-max_bias / n), m1 = 2^(-max_bias / 2 / n), n = 2^floor(log2 n_head))
 template <typename A> static inline void attn_set_softmax(A & a, const attn_call & c) {

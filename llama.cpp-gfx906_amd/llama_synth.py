@@ -105,6 +105,7 @@ def harness():
         L.mi_llama_last_logits.restype = C.c_void_p; L.mi_llama_last_logits.argtypes = [C.c_void_p]
         L.mi_llama_decode.restype = C.c_int
         L.mi_llama_decode.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+        L.mi_llama_decode_batch.restype = C.c_int; L.mi_llama_decode_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int]
         L.mi_llama_synth_embedding.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
         L.mi_llama_graph_nodes.restype = C.c_int; L.mi_llama_graph_nodes.argtypes = [C.c_void_p, C.c_int]
         L.mi_llama_create_from_gguf.restype = C.c_void_p
@@ -188,6 +189,21 @@ class SynthLlama:
         if not sync:
             return out if view else None        # (not complete before the caller synchronizes)
         return out if view else out.copy()
+
+    def decode_batch(self, tokens_per_seq, want_host=True, sync=True):
+        """one llama_decode of a ubatch with equally many tokens for each of the n_seq_max sequences (kv_unified = false: every sequence attends to its own
+        cache stream; tokens_per_seq[s] are sequence s's tokens). Returns every token's logits, [n_seq_max * T, n_vocab], token t of sequence s at row s*T + t"""
+        tok = np.ascontiguousarray(tokens_per_seq, dtype=np.int32)
+        if tok.ndim != 2 or tok.shape[0] != max(1, self.hp.n_seq_max):
+            raise ValueError(f"decode_batch takes one list of tokens per sequence, all of one length: got shape {tok.shape} for {self.hp.n_seq_max} sequences")
+        rc = self.L.mi_llama_decode_batch(self.m, tok.ctypes.data_as(C.c_void_p), tok.shape[1], int(bool(sync)) | (0 if want_host else 2))
+        if rc != 0:
+            raise RuntimeError(f"mi_llama_decode_batch returned {rc}")
+        if not want_host or not sync:
+            return None
+        n_res = self.L.mi_llama_n_result(self.m)
+        out = np.ctypeslib.as_array(C.cast(self.L.mi_llama_last_logits(self.m), C.POINTER(C.c_float)), shape=(n_res,))
+        return out.reshape(tok.size, -1).copy()
 
     def embedding(self, token):
         out = np.empty(self.cfg["n_embd"], dtype=np.float32)
