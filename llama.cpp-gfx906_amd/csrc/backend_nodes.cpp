@@ -572,6 +572,7 @@ static int try_fused_mmv(mi_backend_ctx * c, struct ggml_cgraph * g, int i, int 
         }
         rope_l = *rope; rope_l.table = c->rope_tab; rope = &rope_l;
     }
+    if (!mul_mat_vec_q_fused_takes(grp, nc, K, in, rope)) return -1;      // (Q5_0 / Q5_1 groups the streamed kernel declines: node by node)
     if (c->pass.pp.active && in.mode == PRO_NORM && (const void *) in.x == (const void *) c->pass.pp.x_out && K == c->pass.pp.m) {
         // the norm's input is the MoE combine left pending: this launch evaluates it in its prologue (and stores the sum). EVERY workgroup's prologue reads the
         // residual, the experts' outputs, the router's probabilities and the ids while other workgroups already store their rows — and by graph order all four are
@@ -838,6 +839,7 @@ static int try_fused_moe_experts(mi_backend_ctx * c, struct ggml_cgraph * g, int
                                bg ? (const float *) bg->src[1]->data : nullptr, bu ? (const float *) bu->src[1]->data : nullptr,
                                oai ? op_f32(gl, 2) : 0.0f, oai ? op_f32(gl, 3) : 0.0f };
                 }
+                if (!mul_mat_vec_q_fused_takes(grp, n_used, K, in, nullptr)) return 0;
                 emit_mmv(c, grp, n_used, K, in, nullptr, nullptr, (uint64_t) 2*n_used*M*ggml_row_size(as->type, K));
                 return jg - i + 1;
             }
@@ -860,6 +862,7 @@ static int try_fused_moe_experts(mi_backend_ctx * c, struct ggml_cgraph * g, int
                    bias ? (const float *) bias->data : nullptr, nullptr, nullptr, 0, 0, (const int32_t *) ids->data + u, as->nb[2], b->ne[1] > 1 ? (int)((size_t) u*b->nb[1]/4) : 0 };
         grp[u].res_eid = bias ? 1 : 0;
     }
+    if (!mul_mat_vec_q_fused_takes(grp, n_used, K, in, nullptr)) return 0;
     emit_mmv(c, grp, n_used, K, in, nullptr, nullptr, (uint64_t) n_used*M*ggml_row_size(as->type, K));
     return consumed;
 }

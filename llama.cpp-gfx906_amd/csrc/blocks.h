@@ -12,6 +12,10 @@
 #pragma pack(push, 1)
 // Q4_0: 32 el / 18 B — quants.py:241-251. el j<16 = low nibble of qs[j], j>=16 = high nibble; x = d*(q-8)
 struct block_q4_0 { uint16_t d; uint8_t qs[16]; };
+// Q5_0: 32 el / 22 B — quants.py:291-330. nibbles as Q4_0; bit j of qh (little-endian u32) = 5th bit of el j; x = d*(q-16)
+struct block_q5_0 { uint16_t d; uint8_t qh[4]; uint8_t qs[16]; };
+// Q5_1: 32 el / 24 B — quants.py:333-375. as Q5_0 plus f16 m; x = d*q + m
+struct block_q5_1 { uint16_t d; uint16_t m; uint8_t qh[4]; uint8_t qs[16]; };
 // Q8_0: 32 el / 34 B — quants.py:396-401. x = d*q
 struct block_q8_0 { uint16_t d; int8_t qs[32]; };
 // Q4_K: 256 el / 144 B — quants.py:504-522. 8 sub-blocks of 32; qs in 4 groups of 32 B
@@ -26,6 +30,8 @@ struct block_mxfp4 { uint8_t e; uint8_t qs[16]; };
 #pragma pack(pop)
 
 static_assert(sizeof(block_q4_0)  == 18,  "Q4_0 block size (constants.py:2842)");
+static_assert(sizeof(block_q5_0)  == 22,  "Q5_0 block size (constants.py:2844)");
+static_assert(sizeof(block_q5_1)  == 24,  "Q5_1 block size (constants.py:2845)");
 static_assert(sizeof(block_q8_0)  == 34,  "Q8_0 block size (constants.py:2846)");
 static_assert(sizeof(block_q4_K)  == 144, "Q4_K block size (constants.py:2850)");
 static_assert(sizeof(block_q5_K)  == 176, "Q5_K block size (constants.py:2851)");

@@ -68,6 +68,7 @@ static const type_traits * traits(enum ggml_type t) {
         tt[GGML_TYPE_Q5_K]  = { "q5_K",  256, 176, true  };
         tt[GGML_TYPE_Q6_K]  = { "q6_K",  256, 210, true  };
         tt[GGML_TYPE_Q8_K]  = { "q8_K",  256, 292, true  };
+        tt[GGML_TYPE_IQ4_NL] = { "iq4_nl", 32, 18,  true  };
         tt[GGML_TYPE_MXFP4] = { "mxfp4", 32,  17,  true  };
         init = true;
     }

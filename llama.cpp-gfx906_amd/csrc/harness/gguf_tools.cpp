@@ -29,6 +29,28 @@ bool dequant_row_host(int type, const uint8_t * src, float * dst, int64_t n) {
                 for (int j = 0; j < 16; j++) { dst[b*32 + j] = d*((x->qs[j] & 0xF) - 8); dst[b*32 + 16 + j] = d*((x->qs[j] >> 4) - 8); }
             }
             return true;
+        case GGML_TYPE_Q5_0:
+            for (int64_t b = 0; b < n/32; b++) {
+                const block_q5_0 * x = (const block_q5_0 *) src + b;
+                const float d = ggml_fp16_to_fp32(x->d);
+                uint32_t qh; memcpy(&qh, x->qh, 4);
+                for (int j = 0; j < 16; j++) {
+                    dst[b*32 + j]      = d*((int)((x->qs[j] & 0xF) | (((qh >> j) & 1) << 4)) - 16);
+                    dst[b*32 + 16 + j] = d*((int)((x->qs[j] >> 4)  | (((qh >> (j + 16)) & 1) << 4)) - 16);
+                }
+            }
+            return true;
+        case GGML_TYPE_Q5_1:
+            for (int64_t b = 0; b < n/32; b++) {
+                const block_q5_1 * x = (const block_q5_1 *) src + b;
+                const float d = ggml_fp16_to_fp32(x->d), m = ggml_fp16_to_fp32(x->m);
+                uint32_t qh; memcpy(&qh, x->qh, 4);
+                for (int j = 0; j < 16; j++) {
+                    const float lo = d*(float)((x->qs[j] & 0xF) | (((qh >> j) & 1) << 4)), hi = d*(float)((x->qs[j] >> 4) | (((qh >> (j + 16)) & 1) << 4));
+                    dst[b*32 + j] = lo + m; dst[b*32 + 16 + j] = hi + m;
+                }
+            }
+            return true;
         case GGML_TYPE_Q8_0:
             for (int64_t b = 0; b < n/32; b++) {
                 const block_q8_0 * x = (const block_q8_0 *) src + b;
@@ -173,6 +195,11 @@ GGML_API long long mi_gguf_describe(const char * path, char * buf, long long cap
     }
     if (buf && cap > 0) snprintf(buf, (size_t) cap, "%s", o.c_str());
     return (long long) o.size();
+}
+
+// one row of n elements of `type` at src -> f32 at dst with the host decoder the model path reads token embeddings with; 0: no decoder for the type
+GGML_API int mi_gguf_dequant_row(int type, const void * src, float * dst, long long n) {
+    return dequant_row_host(type, (const uint8_t *) src, dst, (int64_t) n) ? 1 : 0;
 }
 
 } // extern "C"

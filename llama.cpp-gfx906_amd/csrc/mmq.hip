@@ -88,6 +88,29 @@ template <> __device__ __forceinline__ void decode4<T_Q4_0>(const raw32 & r, con
 #pragma unroll
     for (int b = 0; b < 4; b++) o[b] = (float)((int)((q4 >> (8*b)) & 0xFF) - 8)*h.a;
 }
+// Q5_0 / Q5_1 — quants.py:291-375: nibbles as Q4_0, bit j of qh = the fifth bit of element j. r.s = d | m << 16 (Q5_0: d only), word 4 = qh
+static __device__ __forceinline__ uint32_t q5_word(const raw32 & r, int ws, int wi) {      // the four quants [4 wi, 4 wi + 4) as bytes
+    const uint32_t hb = ((uint32_t) r.v[1].x >> (4*wi)) & 0xFu;
+    return ((raw_word(r, ws & 3) >> (4*(wi >> 2))) & 0x0F0F0F0Fu) | ((__umul24(hb, 0x00204081u) & 0x01010101u) << 4);
+}
+template <> __device__ __forceinline__ raw32 load_raw32<T_Q5_0>(const char * row, int c32) {
+    raw32 r; const char * b = row + (size_t) c32*22; r.s = ld_u16(b); r.v[1].x = (int) ld_u32(b + 2); r.v[0] = ld_b128(b + 6); return r;
+}
+template <> __device__ __forceinline__ dq_head decode_head<T_Q5_0>(const raw32 & r, int) { return { f16_bits_to_f32((uint16_t) r.s), 0.0f }; }
+template <> __device__ __forceinline__ void decode4<T_Q5_0>(const raw32 & r, const dq_head & h, int, int ws, int wi, float (&o)[4]) {
+    const uint32_t q5 = q5_word(r, ws, wi);
+#pragma unroll
+    for (int b = 0; b < 4; b++) o[b] = (float)((int)((q5 >> (8*b)) & 0xFF) - 16)*h.a;
+}
+template <> __device__ __forceinline__ raw32 load_raw32<T_Q5_1>(const char * row, int c32) {
+    raw32 r; const char * b = row + (size_t) c32*24; const int2v h = ld_b64(b); r.s = (uint32_t) h.x; r.v[1].x = h.y; r.v[0] = ld_b128(b + 8); return r;
+}
+template <> __device__ __forceinline__ dq_head decode_head<T_Q5_1>(const raw32 & r, int) { return { f16_bits_to_f32((uint16_t)(r.s & 0xFFFF)), f16_bits_to_f32((uint16_t)(r.s >> 16)) }; }
+template <> __device__ __forceinline__ void decode4<T_Q5_1>(const raw32 & r, const dq_head & h, int, int ws, int wi, float (&o)[4]) {
+    const uint32_t q5 = q5_word(r, ws, wi);
+#pragma unroll
+    for (int b = 0; b < 4; b++) o[b] = h.a*(float)((q5 >> (8*b)) & 0xFF) + h.b;
+}
 // Q8_0 — quants.py:396-401
 template <> __device__ __forceinline__ raw32 load_raw32<T_Q8_0>(const char * row, int c32) {
     raw32 r; const char * b = row + (size_t) c32*34; r.s = ld_u16(b); r.v[0] = ld_b128(b + 2); r.v[1] = ld_b128(b + 18); return r;
@@ -480,6 +503,12 @@ __global__ void __launch_bounds__(BN*2) __attribute__((amdgpu_waves_per_eu(2, 2)
 template <int TYPE> static __device__ __forceinline__ raw32 load_raw8(const char * row, int c32, int q);
 template <> __device__ __forceinline__ raw32 load_raw8<T_Q4_0>(const char * row, int c32, int q) {
     raw32 r; const char * b = row + (size_t) c32*18; r.s = ld_u16(b); const int2v t = ld_b64(b + 2 + 8*(q & 1)); r.v[0].x = t.x; r.v[0].y = t.y; return r;
+}
+template <> __device__ __forceinline__ raw32 load_raw8<T_Q5_0>(const char * row, int c32, int q) {
+    raw32 r; const char * b = row + (size_t) c32*22; r.s = ld_u16(b); r.v[1].x = (int) ld_u32(b + 2); const int2v t = ld_b64(b + 6 + 8*(q & 1)); r.v[0].x = t.x; r.v[0].y = t.y; return r;
+}
+template <> __device__ __forceinline__ raw32 load_raw8<T_Q5_1>(const char * row, int c32, int q) {
+    raw32 r; const char * b = row + (size_t) c32*24; const int2v h = ld_b64(b), t = ld_b64(b + 8 + 8*(q & 1)); r.s = (uint32_t) h.x; r.v[1].x = h.y; r.v[0].x = t.x; r.v[0].y = t.y; return r;
 }
 template <> __device__ __forceinline__ raw32 load_raw8<T_MXFP4>(const char * row, int c32, int q) {
     raw32 r; const char * b = row + (size_t) c32*17; r.s = *(const uint8_t *) b; const int2v t = ld_b64(b + 1 + 8*(q & 1)); r.v[0].x = t.x; r.v[0].y = t.y; return r;
@@ -1006,6 +1035,8 @@ template <auto KERNEL> static void mmq_launch(dim3 grid, int block, size_t lds_b
 template <typename F> static void mmq_dispatch_type(int type, const char * who, F && f) {
     switch (type) {
         case T_Q4_0:  f(std::integral_constant<int, T_Q4_0>{});  break;
+        case T_Q5_0:  f(std::integral_constant<int, T_Q5_0>{});  break;
+        case T_Q5_1:  f(std::integral_constant<int, T_Q5_1>{});  break;
         case T_Q8_0:  f(std::integral_constant<int, T_Q8_0>{});  break;
         case T_Q4_K:  f(std::integral_constant<int, T_Q4_K>{});  break;
         case T_Q5_K:  f(std::integral_constant<int, T_Q5_K>{});  break;

@@ -12,7 +12,7 @@
 // Mapping (wave64, no cross-wave communication):
 //   * a workgroup = 4 waves; each wave owns R consecutive weight rows and walks the whole K.
 //   * inside a row, LPB lanes cooperate on one block so that every lane issues ONE 16-byte (Q4_K,
-//     Q5_K, Q8_0, Q4_0, MXFP4) or 3 x 8-byte (Q6_K) load of packed quants per row per step and a
+//     Q5_K, Q8_0, Q4_0, Q5_0, Q5_1, MXFP4) or 3 x 8-byte (Q6_K) load of packed quants per row per step and a
 //     wave-wide load instruction covers 64/LPB consecutive blocks (>= 1 KiB of contiguous HBM).
 //     Loads go straight to VGPRs (cdna_hip_programming.md "GEMV / M <= 16 decode weights": LDS
 //     round trip is pure overhead), nontemporal where the address is 16-byte aligned.
@@ -238,7 +238,7 @@ static bool launch_mmvq_cols(const mmvq_args & a, int act_kind, hipStream_t stre
 // ------------------------------------------------------------------------------------------------
 bool mul_mat_vec_q_supported(int type_a) {
     switch (type_a) {
-        case T_Q4_0: case T_Q8_0: case T_Q4_K: case T_Q5_K: case T_Q6_K: case T_MXFP4: return true;
+        case T_Q4_0: case T_Q5_0: case T_Q5_1: case T_Q8_0: case T_Q4_K: case T_Q5_K: case T_Q6_K: case T_MXFP4: return true;
         default: return false;
     }
 }
@@ -257,6 +257,8 @@ static void launch_mmvq_n(const mmvq_args & a, int act_kind, int64_t n_pairs, hi
     // measured (tools/op_perf.py, m = 4096, k = 14336): faster for the 32-element block formats (Q8_0 n = 8: 57.7 -> 30.4 us, Q4_0 35.9 ->
     // 27.4) but not for the K-quants, whose n dot chains per block are VALU-bound either way (Q4_K n = 8: 29.5 -> 35.5 us with 2 waves
     // per SIMD; 16 waves per workgroup spill) — those keep the simple kernel until the int8 MFMA kernel exists
+    // (not kept: Q5_0 / Q5_1 on this route — same shape, n = 8: 27.8 against 20.9 us and 26.8 against 19.8, equal at n = 2: the five-bit unpack per column makes it
+    // VALU-bound like the K-quants; DESIGN.md §4 "Q5_0 and Q5_1")
     if (NCOLS > 1 && !IDS && a.n_batch <= 1 && (TYPE == T_Q8_0 || TYPE == T_Q4_0)) {
         static const int use_cols = (int) env_int("GGML_MI355X_MMVQ_COLS", 1);
         if (use_cols && launch_mmvq_cols<TYPE, (NCOLS > 1 ? NCOLS : 2)>(a, act_kind, stream)) return;
@@ -283,6 +285,8 @@ template <bool IDS>
 static void launch_mmvq(int type_a, const mmvq_args & a, int act_kind, int64_t n, int64_t n_pairs, hipStream_t stream) {
     switch (type_a) {
         case T_Q4_0:  launch_mmvq_t<T_Q4_0,  IDS>(a, act_kind, n, n_pairs, stream); break;
+        case T_Q5_0:  launch_mmvq_t<T_Q5_0,  IDS>(a, act_kind, n, n_pairs, stream); break;
+        case T_Q5_1:  launch_mmvq_t<T_Q5_1,  IDS>(a, act_kind, n, n_pairs, stream); break;
         case T_Q8_0:  launch_mmvq_t<T_Q8_0,  IDS>(a, act_kind, n, n_pairs, stream); break;
         case T_Q4_K:  launch_mmvq_t<T_Q4_K,  IDS>(a, act_kind, n, n_pairs, stream); break;
         case T_Q5_K:  launch_mmvq_t<T_Q5_K,  IDS>(a, act_kind, n, n_pairs, stream); break;

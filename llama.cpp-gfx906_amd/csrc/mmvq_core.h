@@ -288,6 +288,62 @@ template <> struct mmvq_t<T_Q4_0> {
     }
 };
 
+// ---- Q5_0 / Q5_1 ---------------------------------------------------------------------------------
+// bits 0..3 of x as bit 0 of bytes 0..3 (the four shifted copies of the multiplication do not overlap; both factors fit 24 bits: one full-rate v_mul_u32_u24)
+static __device__ __forceinline__ uint32_t q5_spread4(uint32_t x) { return __umul24(x & 0xFu, 0x00204081u) & 0x01010101u; }
+// the 32 five-bit quants of a block as bytes: lo = elements 0..15 (low nibbles of qs, bits 0..15 of qh), hi = elements 16..31
+static __device__ __forceinline__ void q5_unpack(const int4v & qs, uint32_t qh, int4v & lo, int4v & hi) {
+#define MI_Q5B(c, i) \
+    lo.c = (int)(((uint32_t) qs.c & 0x0F0F0F0Fu)        | (q5_spread4(qh >> (4*(i)))      << 4)); \
+    hi.c = (int)((((uint32_t) qs.c >> 4) & 0x0F0F0F0Fu) | (q5_spread4(qh >> (16 + 4*(i))) << 4));
+    MI_Q5B(x, 0) MI_Q5B(y, 1) MI_Q5B(z, 2) MI_Q5B(w, 3)
+#undef MI_Q5B
+}
+// Q5_0: 22-byte blocks (f16 d | u32 qh | 16 bytes of nibbles), 2-byte aligned; sum (q - 16) a = sum q a - 16 bsum
+template <> struct mmvq_t<T_Q5_0> {
+    static constexpr int LPB = 1, BLOCK_BYTES = 22, QK = 32, ACT = T_Q8_0;
+    typedef mmvq_t<T_Q4_0>::afrag afrag;
+    struct wfrag { int4v qs; uint32_t d, qh; };
+    static __device__ __forceinline__ afrag load_a(const act_view & a, int64_t ib, int slot) { return mmvq_t<T_Q4_0>::load_a(a, ib, slot); }
+    static __device__ __forceinline__ wfrag load_w(const char * row, int64_t ib, int) {
+        const char * b = row + ib*BLOCK_BYTES;
+        wfrag w;
+        w.qs = ld_b128(b + 6);
+        w.d  = ld_u16(b);
+        w.qh = ld_u32(b + 2);
+        return w;
+    }
+    static __device__ __forceinline__ float dot(const wfrag & w, const afrag & a, int) {
+        int4v lo, hi;
+        q5_unpack(w.qs, w.qh, lo, hi);
+        const int sumi = dot16(lo, a.lo) + dot16(hi, a.hi) - 16*a.bs;
+        return ((float) sumi*f16_bits_to_f32((uint16_t) w.d))*a.d8;
+    }
+};
+// Q5_1: 24-byte blocks (f16 d | f16 m | u32 qh | 16 bytes of nibbles), 8-byte aligned; x = d q + m: sumi d d_a + m d_a bsum. (The CPU backend reads
+// s = d_a bsum from a Q8_1 block, rounded to f16; here the product stays in f32.)
+template <> struct mmvq_t<T_Q5_1> {
+    static constexpr int LPB = 1, BLOCK_BYTES = 24, QK = 32, ACT = T_Q8_0;
+    typedef mmvq_t<T_Q4_0>::afrag afrag;
+    struct wfrag { int4v qs; uint32_t dm, qh; };
+    static __device__ __forceinline__ afrag load_a(const act_view & a, int64_t ib, int slot) { return mmvq_t<T_Q4_0>::load_a(a, ib, slot); }
+    static __device__ __forceinline__ wfrag load_w(const char * row, int64_t ib, int) {
+        const char * b = row + ib*BLOCK_BYTES;
+        wfrag w;
+        w.qs = ld_b128(b + 8);
+        const int2v h = ld_b64(b);
+        w.dm = (uint32_t) h.x; w.qh = (uint32_t) h.y;
+        return w;
+    }
+    static __device__ __forceinline__ float dot(const wfrag & w, const afrag & a, int) {
+        int4v lo, hi;
+        q5_unpack(w.qs, w.qh, lo, hi);
+        const int sumi = dot16(lo, a.lo) + dot16(hi, a.hi);
+        const float d = f16_bits_to_f32((uint16_t)(w.dm & 0xFFFF)), m = f16_bits_to_f32((uint16_t)(w.dm >> 16));
+        return ((float) sumi*d)*a.d8 + (m*a.d8)*(float) a.bs;
+    }
+};
+
 // ---- MXFP4 --------------------------------------------------------------------------------------
 // 16-entry int8 lookup (quants.py:659) for 4 packed 4-bit indices with two v_perm_b32 + a bit-select
 static __device__ __forceinline__ int mxfp4_lut4(uint32_t idx) {

@@ -222,6 +222,21 @@ static fused_launch fused_prepare(const mmvq_group * groups, int n_groups, int64
     return L;
 }
 
+// the formats fused_launch_kernel has register-ring kernels for
+static bool fused_ring_has(int type) {
+    switch (type) {
+        case T_Q4_K: case T_Q5_K: case T_Q6_K: case T_Q8_0: case T_Q4_0: case T_MXFP4: return true;
+        default: return false;
+    }
+}
+bool mul_mat_vec_q_fused_takes(const mmvq_group * groups, int n_groups, int64_t k, const mmvq_input & in, const mmvq_rope * rope) {
+    bool ring = true;
+    for (int i = 0; i < n_groups; i++) ring = ring && fused_ring_has(groups[i].type);
+    if (ring) return true;
+    if (in.planes) return false;      // (a pending MoE combine is folded in only after the matcher has asked)
+    return mul_mat_vec_q_stream_plan(groups, n_groups, k, in, rope).ok;
+}
+
 static void fused_launch_kernel(const fused_launch & L, hipStream_t stream) {
     const int ta = L.ta, tb = L.tb;
     if (ta == tb) {

@@ -358,6 +358,90 @@ template <> struct st_unit<T_Q4_0> {
     }
 };
 
+// Q5_0: 22-byte blocks (f16 d | u32 qh | 16 bytes of nibbles as Q4_0's; bit j of qh = the fifth bit of element j; value = q - 16) — a unit is eight of them
+// (176 bytes = 11 chunks: odd, the size Q5_K streams). Block j starts 22 j bytes in: on a dword boundary for even j (d in the low half, qh and the nibbles two bytes
+// off: one v_alignbit per dword), two bytes past one for odd j (d in the high half, qh and the nibbles dword-aligned). Activation: the Q4_0 unit's image.
+// sum (q - 16) a = sum q a - 16 sum a; per block sumi * (d_w * d_a), block after block.
+template <> struct st_unit<T_Q5_0> {
+    static constexpr int UB = 176;
+    struct wfrag { int4v c[11]; };
+    static __device__ __forceinline__ wfrag load(uint32_t a) {
+        wfrag w;
+#pragma unroll
+        for (int j = 0; j < 11; j++) w.c[j] = st_ld16(a + 16*j);
+        return w;
+    }
+    static __device__ __forceinline__ uint32_t dw(const wfrag & w, int i) { return (uint32_t) w.c[i >> 2][i & 3]; }
+    // the dword at byte offset o of the unit (o even, a compile-time constant)
+    static __device__ __forceinline__ uint32_t at(const wfrag & w, int o) { return (o & 2) ? __builtin_amdgcn_alignbit(dw(w, (o >> 2) + 1), dw(w, o >> 2), 16) : dw(w, o >> 2); }
+    static __device__ __forceinline__ float dot(const wfrag & w, const char * ab, float) {
+        float acc = 0.0f;
+        const float4v da0 = *(const float4v *) (ab + 256), da1 = *(const float4v *) (ab + 272);
+        const int4v bsv = *(const int4v *) (ab + 288);
+#pragma unroll
+        for (int j = 0; j < 8; j++) {
+            const int B = 22*j;
+            const uint32_t dbits = (B & 2) ? dw(w, B >> 2) >> 16 : dw(w, B >> 2) & 0xFFFF;
+            const uint32_t qh = at(w, B + 2);
+            const int4v A0 = *(const int4v *) (ab + 32*j), A1 = *(const int4v *) (ab + 32*j + 16);
+            int isum = 0;
+#pragma unroll
+            for (int i = 0; i < 4; i++) {
+                const uint32_t qv = at(w, B + 6 + 4*i);
+                isum = dot4((int)((qv & 0x0F0F0F0Fu)        | (q5_spread4(qh >> (4*i))      << 4)), A0[i], isum);
+                isum = dot4((int)(((qv >> 4) & 0x0F0F0F0Fu) | (q5_spread4(qh >> (16 + 4*i)) << 4)), A1[i], isum);
+            }
+            const uint32_t bw = (uint32_t) bsv[j >> 1];
+            const int bsum = (int)(int16_t)((j & 1) ? bw >> 16 : bw & 0xFFFF);
+            const float da = j < 4 ? da0[j] : da1[j - 4];
+            acc += (float)(isum - 16*bsum)*(f16_bits_to_f32((uint16_t) dbits)*da);
+        }
+        return acc;
+    }
+};
+
+// Q5_1: 24-byte blocks (f16 d | f16 m | u32 qh | 16 bytes of nibbles; value = d q + m) — a unit is eight of them (192 bytes = 12 chunks), every field dword-aligned:
+// block j's dwords are 6 j (d | m), 6 j + 1 (qh), 6 j + 2 .. 6 j + 5 (nibbles). Per block sumi * (d_w * d_a) + (m * d_a) * bsum (mmvq_core.h: the f32 product where
+// the CPU backend reads Q8_1's f16 s).
+// LDS banks: twelve chunks is an EVEN stride — a ds_read_b128 lane group (16 lanes) finds its units' chunk j on the 16-byte bank slots (12 u + j) mod 16, four
+// distinct values: every unit read is a 4-way conflict (the other units' odd chunk counts make theirs conflict-free). Not padded: the loader's LDS-DMA lays a
+// workgroup's rows down as they lie in memory (1 KiB per instruction, mmvq_stream.h's premise), and a read order rotated per lane only moves the conflict to the
+// activation reads (304-byte stride: 3 ib + 4 p mod 16 collides the same way). At 4 x 4 LDS cycles per read a wave spends ~190 cycles on the 12 KiB of a slot,
+// ~60 bytes per clock and CU against the ~10 bytes per clock a CU's share of HBM delivers: the conflict is paid out of idle LDS time (DESIGN.md §4 has the measurement).
+template <> struct st_unit<T_Q5_1> {
+    static constexpr int UB = 192;
+    struct wfrag { int4v c[12]; };
+    static __device__ __forceinline__ wfrag load(uint32_t a) {
+        wfrag w;
+#pragma unroll
+        for (int j = 0; j < 12; j++) w.c[j] = st_ld16(a + 16*j);
+        return w;
+    }
+    static __device__ __forceinline__ uint32_t dw(const wfrag & w, int i) { return (uint32_t) w.c[i >> 2][i & 3]; }
+    static __device__ __forceinline__ float dot(const wfrag & w, const char * ab, float) {
+        float acc = 0.0f;
+        const float4v da0 = *(const float4v *) (ab + 256), da1 = *(const float4v *) (ab + 272);
+        const int4v bsv = *(const int4v *) (ab + 288);
+#pragma unroll
+        for (int j = 0; j < 8; j++) {
+            const uint32_t dm = dw(w, 6*j), qh = dw(w, 6*j + 1);
+            const int4v A0 = *(const int4v *) (ab + 32*j), A1 = *(const int4v *) (ab + 32*j + 16);
+            int isum = 0;
+#pragma unroll
+            for (int i = 0; i < 4; i++) {
+                const uint32_t qv = dw(w, 6*j + 2 + i);
+                isum = dot4((int)((qv & 0x0F0F0F0Fu)        | (q5_spread4(qh >> (4*i))      << 4)), A0[i], isum);
+                isum = dot4((int)(((qv >> 4) & 0x0F0F0F0Fu) | (q5_spread4(qh >> (16 + 4*i)) << 4)), A1[i], isum);
+            }
+            const uint32_t bw = (uint32_t) bsv[j >> 1];
+            const int bsum = (int)(int16_t)((j & 1) ? bw >> 16 : bw & 0xFFFF);
+            const float da = j < 4 ? da0[j] : da1[j - 4];
+            acc += (float) isum*(f16_bits_to_f32((uint16_t)(dm & 0xFFFF))*da) + (f16_bits_to_f32((uint16_t)(dm >> 16))*da)*(float) bsum;
+        }
+        return acc;
+    }
+};
+
 // ---- ten-block units (k % 256 != 0) ----
 // Q8_0: 340 bytes = 85 dwords, dword-aligned in the slot (odd number of dwords: conflict-free ds_read_b32). Block j: d at byte 34 j, quants at 34 j + 2.
 template <> struct st_unit<ST_Q8_0_B10> {
@@ -567,7 +651,7 @@ static __device__ __forceinline__ void st_prologue_q8(const st_args & p, const s
 // PRO_QUANT / PRO_NORM: x (f32) -> [RMS_NORM * w ->] Q8_K blocks, quant_core.h's arithmetic. Consumer wave w owns the 256-element chunks
 // w, w + 8, ...: NA of them, all quantized in straight-line code (a chunk past the end is a clamped duplicate that is not stored) so that
 // the dependent chains of the wave-wide maxima and sums interleave — chunk after chunk behind a branch each cost ~0.5 us per chunk
-// IMG: 0 = Q8_K blocks (K-quant weights); 1 = the workgroup's weights are Q8_0 in 256-weight units — the image is the CPU path's Q8_0 instead (32-element
+// IMG: 0 = Q8_K blocks (K-quant weights); 1 = the workgroup's weights are Q8_0 / Q4_0 / Q5_0 / Q5_1 in 256-weight units — the image is the CPU path's Q8_0 instead (32-element
 // blocks, f16-rounded scales: quant_core.h); 2 = the same Q8_0 activation for the ten-block units (k % 256 != 0: the last 256-piece is partial)
 template <int NA, int IMG, bool NORM>
 static __device__ __forceinline__ void st_prologue_f32(const st_args & p, const st_lds & L, int x_off, int lane, int wave) {
@@ -703,7 +787,7 @@ static __device__ __forceinline__ void st_prologue_f32(const st_args & p, const 
             }
             char * ab = L.act + (size_t) c*ST_ACT_STRIDE;
             *(uint32_t *) (ab + lane*4) = q4[i];
-            if (Q80) { if ((lane & 7) == 0) { ((float *) (ab + 256))[lane >> 3] = d8[i]; ((int16_t *) (ab + 288))[lane >> 3] = (int16_t) bs16[i]; } continue; }      // (the sums: Q4_0's - 8 offset)
+            if (Q80) { if ((lane & 7) == 0) { ((float *) (ab + 256))[lane >> 3] = d8[i]; ((int16_t *) (ab + 288))[lane >> 3] = (int16_t) bs16[i]; } continue; }      // (the sums: Q4_0's - 8 and Q5_0's - 16 offset, Q5_1's m)
             // the 16-element sum of quad q = lane >> 2 (valid in its four lanes); the 32-element sum j at lane 8j + 4 (row_shr:4 brings lane 8j's)
             const int bs32 = bs16[i] + dpp_i<0x114>(bs16[i]);
             int h, l;
@@ -850,7 +934,7 @@ static __device__ __forceinline__ void st_consumers(const st_args & p, const st_
 
     // ---- the activation image (its loads are requested before any weight is — a CU returns loads in request order) ----
     const int mode = p.mode;
-    constexpr int ST_IMG = TYPE == ST_MXFP4_B10 ? 3 : TYPE == ST_Q8_0_B10 ? 2 : (TYPE == T_Q8_0 || TYPE == T_Q4_0) ? 1 : 0;
+    constexpr int ST_IMG = TYPE == ST_MXFP4_B10 ? 3 : TYPE == ST_Q8_0_B10 ? 2 : (TYPE == T_Q8_0 || TYPE == T_Q4_0 || TYPE == T_Q5_0 || TYPE == T_Q5_1) ? 1 : 0;
     if (mode == PRO_Q8) st_prologue_q8(p, L, ctid);
     else if (ST_IMG == 0 && !p.planes && p.x && !(p.early & 0x100) && p.nchunk <= 128) {      // (bit 8 of `early`: GGML_MI355X_STREAM_Q16=0, the one-block-per-wave quantizer)
         if (mode == PRO_NORM) {

@@ -27,7 +27,7 @@ struct st_pair { int ta, tb, ub_a, ub_b; st_launch_fn glu, plain; };
 #define ST_SAME(T_)      { T_, T_, st_unit<T_>::UB, st_unit<T_>::UB, st_launch_t<T_, T_, true>, st_launch_t<T_, T_, false> }
 #define ST_MIXED(A_, B_) { A_, B_, st_unit<A_>::UB, st_unit<B_>::UB, nullptr, st_launch_t<A_, B_, false> }
 static const st_pair st_pairs[] = {
-    ST_SAME(T_Q4_K), ST_SAME(T_Q5_K), ST_SAME(T_Q6_K), ST_SAME(ST_Q8_0_B10), ST_SAME(ST_MXFP4_B10), ST_SAME(T_Q4_0), ST_SAME(T_Q8_0),
+    ST_SAME(T_Q4_K), ST_SAME(T_Q5_K), ST_SAME(T_Q6_K), ST_SAME(ST_Q8_0_B10), ST_SAME(ST_MXFP4_B10), ST_SAME(T_Q4_0), ST_SAME(T_Q8_0), ST_SAME(T_Q5_0), ST_SAME(T_Q5_1),
     ST_MIXED(T_Q8_0, T_Q4_K), ST_MIXED(T_Q8_0, T_Q6_K), ST_MIXED(T_Q4_K, T_Q5_K), ST_MIXED(T_Q4_K, T_Q6_K), ST_MIXED(T_Q5_K, T_Q6_K),
 };
 #undef ST_SAME
@@ -98,7 +98,7 @@ st_plan mul_mat_vec_q_stream_plan(const mmvq_group * groups, int n_groups, int64
     for (int i = 0; i < n_groups; i++) {
         const mmvq_group & g = groups[i];
         ut[i] = st_utype(g.type, k); ub[i] = st_unit_bytes(ut[i]);
-        if (!ub[i] || ((g.type == T_Q8_0 || g.type == T_Q4_0) && in.mode == PRO_Q8)) return P;
+        if (!ub[i] || (act_kind_for(g.type) == T_Q8_0 && in.mode == PRO_Q8)) return P;      // (Q8_0, Q4_0, Q5_0, Q5_1 units read the Q8_0 image only the launch's own prologue builds)
         if (ut[i] != ta && ut[i] != tb) { if (ta < 0) ta = ut[i]; else if (tb < 0) tb = ut[i]; else return P; }
         if (b10 && tb >= 0) return P;                              // (one kernel per ten-block format: no mixed launches)
         if ((g.b_gate != nullptr) != (g.b_up != nullptr) || (g.b_gate && (g.epi != EPI_GLU || !g.eid)) || (g.res_eid && (g.epi != EPI_ADD || !g.eid))) return P;

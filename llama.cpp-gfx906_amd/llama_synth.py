@@ -111,6 +111,7 @@ def harness():
         L.mi_llama_create_from_gguf.restype = C.c_void_p
         L.mi_llama_create_from_gguf.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(hparams), C.c_char_p, C.c_int]
         L.mi_gguf_describe.restype = C.c_longlong; L.mi_gguf_describe.argtypes = [C.c_char_p, C.c_char_p, C.c_longlong]
+        L.mi_gguf_dequant_row.restype = C.c_int; L.mi_gguf_dequant_row.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_longlong]
         _hz = L
     return _hz
 

@@ -1,7 +1,11 @@
 """op_perf.py — the reference's own MUL_MAT perf cases (tests/test-backend-ops.cpp:6190-6196: type_a x F32, m = 4096, k = 14336,
 n in {1, 2, 3, 4, 5, 8, 512} — a Llama-3-8B ffn_down) plus the MoE cases (:6226-6229 shapes: MUL_MAT_ID 2880 x 2880, 32 experts top-4,
 and Mixtral's 8 experts top-2) through the backend's C-ABI. n <= 8 reports GB/s of weight bytes (memory-bound), n = 512 TFLOP/s.
-Wall clock over back-to-back graph computes (each case is its own one-node graph, as in test-backend-ops' perf mode)."""
+Wall clock over back-to-back graph computes (each case is its own one-node graph, as in test-backend-ops' perf mode).
+Q5_0 / Q5_1 (not in the oracle's six formats) are quantized by tests/test_q5_formats.py.
+    op_perf.py OUT.json                      every case
+    op_perf.py OUT.json --fa-only            only the FLASH_ATTN_EXT cases
+    op_perf.py OUT.json --types=q5_0,q5_K    only the MUL_MAT cases of these formats"""
 import json
 import sys
 import time
@@ -11,34 +15,43 @@ import numpy as np
 sys.path.insert(0, "tests"); sys.path.insert(0, "oracle"); sys.path.insert(0, ".")
 import oracle as orc
 from gpu_util import QTYPES, backend, gg
+from test_q5_formats import NAMES as Q5_NAMES, QUANT as Q5_QUANT
 
 L = gg.base(); be = backend()
 out = []
 
 
-def timed(g, reps):
+def timed(g, reps, windows=1):
+    """microseconds per compute: the median of `windows` timed windows of `reps` back-to-back computes each (ending in a synchronise)"""
     for _ in range(3):
         be.compute_async(g)
     be.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(reps):
-        be.compute_async(g)
-    be.synchronize()
-    return (time.perf_counter() - t0) / reps * 1e6
+    us = []
+    for _ in range(windows):
+        t0 = time.perf_counter()
+        for _ in range(reps):
+            be.compute_async(g)
+        be.synchronize()
+        us.append((time.perf_counter() - t0) / reps * 1e6)
+    return sorted(us)[len(us) // 2]
 
 
-FA_ONLY = "--fa-only" in sys.argv[2:]      # op_perf.py OUT.json --fa-only: only the FLASH_ATTN_EXT cases
+FA_ONLY = "--fa-only" in sys.argv[2:]
+ONLY_TYPES = [a.split("=", 1)[1].split(",") for a in sys.argv[2:] if a.startswith("--types=")]
+MM_TYPES = dict(QTYPES, q5_0=gg.Q5_0, q5_1=gg.Q5_1)
 
-for name in ([] if FA_ONLY else QTYPES):
+for name in ([] if FA_ONLY else (ONLY_TYPES[0] if ONLY_TYPES else MM_TYPES)):
     m, k = 4096, 14336
     rng = np.random.default_rng(1234)
-    wb = orc.random_blocks(rng, QTYPES[name], (m,), k)
+    if name in Q5_NAMES: wb = Q5_QUANT[Q5_NAMES[name]](rng.uniform(-1, 1, size=(m, k)).astype(np.float32))
+    else: wb = orc.random_blocks(rng, QTYPES[name], (m,), k)
     for n in (1, 2, 3, 4, 5, 8, 512):
         with gg.Context() as ctx:
-            w = ctx.new_tensor(QTYPES[name], [k, m]); b = ctx.new_tensor(gg.F32, [k, n])
+            w = ctx.new_tensor(MM_TYPES[name], [k, m]); b = ctx.new_tensor(gg.F32, [k, n])
             o = L.ggml_mul_mat(ctx.ctx, w, b)
             ctx.alloc(be); gg.tensor_set(w, wb); gg.tensor_set(b, rng.uniform(-1, 1, size=(n, k)).astype(np.float32))
-            us = timed(gg.graph_of(ctx, o), 50 if n <= 8 else 20)
+            # (--types: a comparison between formats or switches — five windows of ten times the computes, the median)
+            us = timed(gg.graph_of(ctx, o), (500 if n <= 8 else 100) if ONLY_TYPES else (50 if n <= 8 else 20), 5 if ONLY_TYPES else 1)
         e = {"op": "MUL_MAT", "type_a": name, "m": m, "k": k, "n": n, "us": round(us, 2)}
         if n <= 8:
             e["GBps_weights"] = round(wb.nbytes / us / 1e3, 1)
@@ -46,7 +59,7 @@ for name in ([] if FA_ONLY else QTYPES):
             e["TFLOPs"] = round(2.0 * m * k * n / us / 1e6, 1)
         out.append(e); print(e, flush=True)
 
-for name, (k, m, n_exp, n_used) in ([] if FA_ONLY else [("mxfp4", (2880, 2880, 32, 4)), ("q4_K", (4096, 14336, 8, 2)), ("q4_K", (14336, 4096, 8, 2))]):
+for name, (k, m, n_exp, n_used) in ([] if FA_ONLY or ONLY_TYPES else [("mxfp4", (2880, 2880, 32, 4)), ("q4_K", (4096, 14336, 8, 2)), ("q4_K", (14336, 4096, 8, 2))]):
     rng = np.random.default_rng(99)
     wb = orc.random_blocks(rng, QTYPES[name], (n_exp, m), k)
     for n in (1, 512):
@@ -68,7 +81,7 @@ for name, (k, m, n_exp, n_used) in ([] if FA_ONLY else [("mxfp4", (2880, 2880, 3
 # FLASH_ATTN_EXT perf cases (tests/test-backend-ops.cpp:6210-6216): head size 64 / 128, 8 KV heads, nr = 1 / 4 query heads per KV head, kv = 4096 / 8192 / 16384
 # cached cells, ONE token, f16 K / V, f16 mask; GB/s = K + V bytes read once per launch. The reference lists head sizes 64 and 128 only: the other
 # (K, V) sizes the backend accepts — 80, 96, 192/128, 192, 256 — are this project's addition to that grid, in the same shape.
-for kv in (4096, 8192, 16384):
+for kv in ([] if ONLY_TYPES else (4096, 8192, 16384)):
     for hs, hsv in ((64, 64), (80, 80), (96, 96), (128, 128), (192, 128), (192, 192), (256, 256)):
         for nr in (1, 4):
             rng = np.random.default_rng(5)
