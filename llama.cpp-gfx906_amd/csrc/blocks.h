@@ -18,6 +18,9 @@ struct block_q5_0 { uint16_t d; uint8_t qh[4]; uint8_t qs[16]; };
 struct block_q5_1 { uint16_t d; uint16_t m; uint8_t qh[4]; uint8_t qs[16]; };
 // Q8_0: 32 el / 34 B — quants.py:396-401. x = d*q
 struct block_q8_0 { uint16_t d; int8_t qs[32]; };
+// Q3_K: 256 el / 110 B — quants.py:431-472. el 128n + 32j + l: low 2 bits = (qs[32n + l] >> 2j) & 3, bit 4n + j of hmask[l] SET = no -4 offset; sixteen 6-bit
+// scales (16 elements each, value sc - 32) packed in 12 bytes, f16 d LAST; x = (d*(sc-32))*q
+struct block_q3_K { uint8_t hmask[32]; uint8_t qs[64]; uint8_t scales[12]; uint16_t d; };
 // Q4_K: 256 el / 144 B — quants.py:504-522. 8 sub-blocks of 32; qs in 4 groups of 32 B
 // (low nibble = sub-block 2g, high = 2g+1); x = d*sc*q - dmin*m, sc/m 6-bit (quants.py:479-501)
 struct block_q4_K { uint16_t d; uint16_t dmin; uint8_t scales[MI_K_SCALE_SIZE]; uint8_t qs[MI_QK_K/2]; };
@@ -33,6 +36,7 @@ static_assert(sizeof(block_q4_0)  == 18,  "Q4_0 block size (constants.py:2842)")
 static_assert(sizeof(block_q5_0)  == 22,  "Q5_0 block size (constants.py:2844)");
 static_assert(sizeof(block_q5_1)  == 24,  "Q5_1 block size (constants.py:2845)");
 static_assert(sizeof(block_q8_0)  == 34,  "Q8_0 block size (constants.py:2846)");
+static_assert(sizeof(block_q3_K)  == 110, "Q3_K block size (constants.py:2849)");
 static_assert(sizeof(block_q4_K)  == 144, "Q4_K block size (constants.py:2850)");
 static_assert(sizeof(block_q5_K)  == 176, "Q5_K block size (constants.py:2851)");
 static_assert(sizeof(block_q6_K)  == 210, "Q6_K block size (constants.py:2852)");

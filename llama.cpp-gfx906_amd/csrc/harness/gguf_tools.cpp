@@ -58,6 +58,21 @@ bool dequant_row_host(int type, const uint8_t * src, float * dst, int64_t n) {
                 for (int j = 0; j < 32; j++) dst[b*32 + j] = d*x->qs[j];
             }
             return true;
+        case GGML_TYPE_Q3_K:
+            for (int64_t b = 0; b < n/256; b++) {
+                const block_q3_K * x = (const block_q3_K *) src + b;
+                const float d = ggml_fp16_to_fp32(x->d);
+                for (int g = 0; g < 16; g++) {                  // quants.py:431-472: sixteen groups of 16 elements, group g = 8n + 2j + l/16
+                    const int sc = (int)(((x->scales[g % 8] >> (4*(g/8))) & 0xF) | (((x->scales[8 + g % 4] >> (2*(g/4))) & 3) << 4)) - 32;
+                    const float dl = d*(float) sc;
+                    const int n2 = g/8, j = (g/2) % 4, l0 = 16*(g % 2);
+                    for (int l = l0; l < l0 + 16; l++) {
+                        const int q = (int)((x->qs[32*n2 + l] >> (2*j)) & 3) - (((x->hmask[l] >> (4*n2 + j)) & 1) ? 0 : 4);
+                        dst[b*256 + 128*n2 + 32*j + l] = dl*(float) q;
+                    }
+                }
+            }
+            return true;
         case GGML_TYPE_Q4_K:
             for (int64_t b = 0; b < n/256; b++) {
                 const block_q4_K * x = (const block_q4_K *) src + b;

@@ -236,7 +236,7 @@ enum ggml_type file_type(mi_llama * m, enum ggml_type type, int64_t ne0, int64_t
     }
     const enum ggml_type ft = (enum ggml_type) ti->type;
     const bool ok = f32_only ? ft == GGML_TYPE_F32
-                             : (ft == GGML_TYPE_Q4_0 || ft == GGML_TYPE_Q5_0 || ft == GGML_TYPE_Q5_1 || ft == GGML_TYPE_Q8_0 || ft == GGML_TYPE_Q4_K || ft == GGML_TYPE_Q5_K || ft == GGML_TYPE_Q6_K ||
+                             : (ft == GGML_TYPE_Q4_0 || ft == GGML_TYPE_Q5_0 || ft == GGML_TYPE_Q5_1 || ft == GGML_TYPE_Q8_0 || ft == GGML_TYPE_Q3_K || ft == GGML_TYPE_Q4_K || ft == GGML_TYPE_Q5_K || ft == GGML_TYPE_Q6_K ||
                                 ft == GGML_TYPE_MXFP4 || ft == GGML_TYPE_F16 || ft == GGML_TYPE_F32);
     if (!ok) throw std::runtime_error(std::string("tensor '") + name + "' has type " + std::to_string((int) ti->type) + ", which this path does not run");
     return ft;

@@ -19,7 +19,7 @@ namespace mi355x {
 
 // ggml_type ids used on the path (gguf-py/gguf/constants.py:2698-2730)
 enum : int {
-    T_F32 = 0, T_F16 = 1, T_Q4_0 = 2, T_Q5_0 = 6, T_Q5_1 = 7, T_Q8_0 = 8, T_Q4_K = 12, T_Q5_K = 13, T_Q6_K = 14, T_Q8_K = 15,
+    T_F32 = 0, T_F16 = 1, T_Q4_0 = 2, T_Q5_0 = 6, T_Q5_1 = 7, T_Q8_0 = 8, T_Q3_K = 11, T_Q4_K = 12, T_Q5_K = 13, T_Q6_K = 14, T_Q8_K = 15,
     T_I32 = 26, T_I64 = 27, T_BF16 = 30, T_MXFP4 = 39,
 };
 
@@ -351,7 +351,7 @@ void mul_mat_vec_q_fused(const mmvq_group * groups, int n_groups, int64_t k, con
 bool mul_mat_vec_q_stream_enabled(void);       // GGML_MI355X_STREAM (default 1)
 bool mul_mat_vec_q_stream_takes(const mmvq_group * groups, int n_groups, int64_t k, const mmvq_input & in, const mmvq_rope * rope);     // = the launch's plan is ok (mmvq_stream.h: st_plan)
 // may this grouped launch be handed to mul_mat_vec_q_fused at all: every group's format has a register-ring kernel (mmvq_fused_<format>.hip), or the streamed kernel
-// takes the launch as it stands. Q5_0 / Q5_1 have no register-ring kernels: a matcher asks this before it emits and runs the nodes one by one on false
+// takes the launch as it stands. Q5_0 / Q5_1 / Q3_K have no register-ring kernels: a matcher asks this before it emits and runs the nodes one by one on false
 bool mul_mat_vec_q_fused_takes(const mmvq_group * groups, int n_groups, int64_t k, const mmvq_input & in, const mmvq_rope * rope);
 bool mul_mat_vec_q_fused_fin_supported(int64_t m, int64_t k_in);   // may a GLU launch with m output rows carry an mmvq_fin
 

@@ -155,6 +155,33 @@ static __device__ __forceinline__ int4v decode8_bf16_mxfp4(const raw32 & r, cons
     }
     return int4v{ (int) out[0], (int) out[1], (int) out[2], (int) out[3] };
 }
+// Q3_K — quants.py:431-472. chunk c of a 256-superblock: half n = c>>2, quarter j = c&3: elements 128n + 32j + l = (qs[32n + l] >> 2j) & 3 | bit c of hmask[l] << 2,
+// minus 4; its two 16-element groups 2c, 2c + 1 have the scales' low nibbles in the byte pair 2j (nibble n) and their top two bits in the byte pair 8 + 2(c&1)
+// (bits 2(c>>1)). Vectors 0, 1 = qs, 2, 3 = hmask; word 16 = those two byte pairs (low | high << 16); r.s = d
+static __device__ __forceinline__ uint32_t q3k_scale_pairs(const char * b, int c) {
+    return (uint32_t) ld_u16(b + 96 + 2*(c & 3)) | ((uint32_t) ld_u16(b + 104 + 2*(c & 1)) << 16);
+}
+template <> __device__ __forceinline__ raw32 load_raw32<T_Q3_K>(const char * row, int c32) {
+    raw32 r; const int c = c32 & 7, n = c >> 2; const char * b = row + (size_t)(c32 >> 3)*110;   // 2-byte aligned only
+    r.v[0] = ld_b128(b + 32 + 32*n); r.v[1] = ld_b128(b + 32 + 32*n + 16); r.v[2] = ld_b128(b); r.v[3] = ld_b128(b + 16);
+    r.v[4].x = (int) q3k_scale_pairs(b, c); r.s = ld_u16(b + 108);
+    return r;
+}
+template <> __device__ __forceinline__ dq_head decode_head<T_Q3_K>(const raw32 & r, int c32) {
+    // branch-free (as k4_sc_m): shifts by 4n and 2(c>>1) only
+    const int c = c32 & 7;
+    const uint32_t lo = ((uint32_t) r.v[4].x & 0xFFFF) >> (4*(c >> 2)), hi = ((uint32_t) r.v[4].x >> 16) >> (2*(c >> 1));
+    const int s0 = (int)((lo & 0xF) | ((hi & 3) << 4)) - 32, s1 = (int)(((lo >> 8) & 0xF) | (((hi >> 8) & 3) << 4)) - 32;
+    const float d = f16_bits_to_f32((uint16_t) r.s);
+    return { d*(float) s0, d*(float) s1 };
+}
+template <> __device__ __forceinline__ void decode4<T_Q3_K>(const raw32 & r, const dq_head & h, int c32, int ws, int wi, float (&o)[4]) {
+    const int c = c32 & 7;       // word-wise: 4 quants per word = 2-bit fields | (bit c of the hmask bytes) << 2, each 0..7
+    const uint32_t q3 = ((raw_word(r, ws) >> (2*(c & 3))) & 0x03030303u) | (((raw_word(r, 8 + ws) >> c) & 0x01010101u) << 2);
+    const float sc = wi < 4 ? h.a : h.b;
+#pragma unroll
+    for (int b = 0; b < 4; b++) o[b] = sc*(float)((int)((q3 >> (8*b)) & 0xFF) - 4);
+}
 // Q4_K — quants.py:504-522
 template <> __device__ __forceinline__ raw32 load_raw32<T_Q4_K>(const char * row, int c32) {
     raw32 r; const int sb = c32 & 7; const char * b = row + (size_t)(c32 >> 3)*144;
@@ -526,6 +553,13 @@ template <> __device__ __forceinline__ raw32 load_raw8<T_Q5_K>(const char * row,
     r.v[0] = *(const int4v *) b; r.s = 0;
     const int2v h = *(const int2v *) (b + 16 + 8*q), t = *(const int2v *) (b + 48 + 32*(sb >> 1) + 8*q);
     r.v[1].x = h.x; r.v[1].y = h.y; r.v[3].x = t.x; r.v[3].y = t.y; return r;
+}
+template <> __device__ __forceinline__ raw32 load_raw8<T_Q3_K>(const char * row, int c32, int q) {
+    raw32 r; const int c = c32 & 7, n = c >> 2; const char * b = row + (size_t)(c32 >> 3)*110;   // 2-byte aligned only
+    const int2v l = ld_b64(b + 32 + 32*n + 8*q), h = ld_b64(b + 8*q);
+    r.v[0].x = l.x; r.v[0].y = l.y; r.v[2].x = h.x; r.v[2].y = h.y;
+    r.v[4].x = (int) q3k_scale_pairs(b, c); r.s = ld_u16(b + 108);
+    return r;
 }
 template <> __device__ __forceinline__ raw32 load_raw8<T_Q6_K>(const char * row, int c32, int q) {
     raw32 r; const int c = c32 & 7, n = c >> 2, pq = c & 3; const char * b = row + (size_t)(c32 >> 3)*210;   // 2-byte aligned only
@@ -1038,6 +1072,7 @@ template <typename F> static void mmq_dispatch_type(int type, const char * who, 
         case T_Q5_0:  f(std::integral_constant<int, T_Q5_0>{});  break;
         case T_Q5_1:  f(std::integral_constant<int, T_Q5_1>{});  break;
         case T_Q8_0:  f(std::integral_constant<int, T_Q8_0>{});  break;
+        case T_Q3_K:  f(std::integral_constant<int, T_Q3_K>{});  break;
         case T_Q4_K:  f(std::integral_constant<int, T_Q4_K>{});  break;
         case T_Q5_K:  f(std::integral_constant<int, T_Q5_K>{});  break;
         case T_Q6_K:  f(std::integral_constant<int, T_Q6_K>{});  break;

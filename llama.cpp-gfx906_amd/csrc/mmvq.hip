@@ -238,7 +238,7 @@ static bool launch_mmvq_cols(const mmvq_args & a, int act_kind, hipStream_t stre
 // ------------------------------------------------------------------------------------------------
 bool mul_mat_vec_q_supported(int type_a) {
     switch (type_a) {
-        case T_Q4_0: case T_Q5_0: case T_Q5_1: case T_Q8_0: case T_Q4_K: case T_Q5_K: case T_Q6_K: case T_MXFP4: return true;
+        case T_Q4_0: case T_Q5_0: case T_Q5_1: case T_Q8_0: case T_Q3_K: case T_Q4_K: case T_Q5_K: case T_Q6_K: case T_MXFP4: return true;
         default: return false;
     }
 }
@@ -288,6 +288,7 @@ static void launch_mmvq(int type_a, const mmvq_args & a, int act_kind, int64_t n
         case T_Q5_0:  launch_mmvq_t<T_Q5_0,  IDS>(a, act_kind, n, n_pairs, stream); break;
         case T_Q5_1:  launch_mmvq_t<T_Q5_1,  IDS>(a, act_kind, n, n_pairs, stream); break;
         case T_Q8_0:  launch_mmvq_t<T_Q8_0,  IDS>(a, act_kind, n, n_pairs, stream); break;
+        case T_Q3_K:  launch_mmvq_t<T_Q3_K,  IDS>(a, act_kind, n, n_pairs, stream); break;
         case T_Q4_K:  launch_mmvq_t<T_Q4_K,  IDS>(a, act_kind, n, n_pairs, stream); break;
         case T_Q5_K:  launch_mmvq_t<T_Q5_K,  IDS>(a, act_kind, n, n_pairs, stream); break;
         case T_Q6_K:  launch_mmvq_t<T_Q6_K,  IDS>(a, act_kind, n, n_pairs, stream); break;

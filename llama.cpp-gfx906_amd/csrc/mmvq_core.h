@@ -234,6 +234,74 @@ template <> struct mmvq_t<T_Q6_K> {
 };
 #endif
 
+// ---- Q3_K ---------------------------------------------------------------------------------------
+// four 6-bit scales (one per byte, 0..63) minus 32 as four signed bytes: flip bit 5, and where it is then set (the value was below 32) set bits 6 and 7 too
+static __device__ __forceinline__ uint32_t q3k_sc_m32(uint32_t lo4, uint32_t hi2) {
+    const uint32_t y = (lo4 | (hi2 << 4)) ^ 0x20202020u;
+    return y | ((y & 0x20202020u)*6u);
+}
+// the sixteen scales of a block as signed bytes, scale g in byte g % 4 of word g / 4 (quants.py:431-472; s0..s2 = the 12 scale bytes as little-endian dwords):
+// low four bits = nibble g / 8 of byte g % 8, top two = bits 2 (g / 4) of byte 8 + g % 4
+static __device__ __forceinline__ void q3k_scales(uint32_t s0, uint32_t s1, uint32_t s2, uint32_t (&sc)[4]) {
+    sc[0] = q3k_sc_m32( s0       & 0x0F0F0F0Fu,  s2       & 0x03030303u);
+    sc[1] = q3k_sc_m32( s1       & 0x0F0F0F0Fu, (s2 >> 2) & 0x03030303u);
+    sc[2] = q3k_sc_m32((s0 >> 4) & 0x0F0F0F0Fu, (s2 >> 4) & 0x03030303u);
+    sc[3] = q3k_sc_m32((s1 >> 4) & 0x0F0F0F0Fu, (s2 >> 6) & 0x03030303u);
+}
+// Four lanes per 110-byte block, the split of Q6_K above: lane slot s: half n = s>>1 (128 elements), l0 = 16*(s&1). The lane owns l = l0..l0+15 of that half:
+// ONE 16-byte run of qs (qs[32n + l], whose four 2-bit fields are elements 128n + 32j + l, j = 0..3) and ONE 16-byte run of hmask (hmask[l], bit 4n + j), so
+// every (j, lane) pair is one contiguous run of 16 int8 activations — exactly the 16-element group g = 8n + 2j + (s&1) of one scale and one Q8_K bsum.
+// (Eight lanes per block would halve the runs to 8 bytes — the 8-byte loads Q6_K's eight-lane split measured slower — and two lanes would leave a wave
+// covering 32 blocks per step, more than a 4096-long row has.) Rows are 110 nb bytes, 2-byte aligned: unaligned-mode loads as Q6_K's.
+// The 12 scale bytes and d are the block's last 14 bytes: one 16-byte load of bytes 94..109 (the last two of qs in front) stays inside the block.
+// sum q a with q = u - 4, u = low | high << 2 in 0..7: dot(u, a) - 4 bsum16 per group (no dmin term).
+template <> struct mmvq_t<T_Q3_K> {
+    static constexpr int LPB = 4, BLOCK_BYTES = 110, QK = 256, ACT = T_Q8_K;
+    struct afrag { int4v a[4]; int s[4]; float d8; };   // s[j] = the Q8_K 16-element sum of a[j]
+    struct wfrag { int4v qs, hm, tail; };
+    static __device__ __forceinline__ afrag load_a(const act_view & a, int64_t ib, int slot) {
+        const int n = slot >> 1, h = slot & 1;
+        afrag f;
+        const int8_t * p = a.qs + ib*256 + 128*n + 16*h;
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            f.a[j] = lds_or_global_b128(p + 32*j);
+            f.s[j] = a.bs[ib*16 + 8*n + 2*j + h];
+        }
+        f.d8 = a.d[ib];
+        return f;
+    }
+    static __device__ __forceinline__ wfrag load_w(const char * row, int64_t ib, int slot) {
+        const int n = slot >> 1, l0 = 16*(slot & 1);
+        const char * b = row + ib*BLOCK_BYTES;   // only 2-byte aligned: unaligned-mode global loads
+        wfrag w;
+        w.qs   = ld_b128(b + 32 + 32*n + l0);
+        w.hm   = ld_b128(b + l0);
+        w.tail = ld_b128(b + 94);                // qs[62..63] | scales[12] | d
+        return w;
+    }
+    static __device__ __forceinline__ float dot(const wfrag & w, const afrag & a, int slot) {
+        const int n = slot >> 1, h = slot & 1;
+        const uint32_t t0 = (uint32_t) w.tail.x, t1 = (uint32_t) w.tail.y, t2 = (uint32_t) w.tail.z, t3 = (uint32_t) w.tail.w;
+        uint32_t scw[4];
+        q3k_scales(__builtin_amdgcn_alignbit(t1, t0, 16), __builtin_amdgcn_alignbit(t2, t1, 16), __builtin_amdgcn_alignbit(t3, t2, 16), scw);
+        // this lane's groups 8n + 2j + h: byte 2 (j & 1) + h of word 2n + (j >> 1)
+        const uint32_t sa = (n ? scw[2] : scw[0]) >> (8*h), sb = (n ? scw[3] : scw[1]) >> (8*h);
+        const int sc0 = (int8_t)(sa & 0xFF), sc1 = (int8_t)((sa >> 16) & 0xFF), sc2 = (int8_t)(sb & 0xFF), sc3 = (int8_t)((sb >> 16) & 0xFF);
+        int acc[4] = { 0, 0, 0, 0 };
+#define MI_Q3(c) { \
+        const uint32_t q = (uint32_t) w.qs.c, hm = (uint32_t) w.hm.c >> (4*n); \
+        acc[0] = dot4((int)(( q       & 0x03030303u) | (( hm       & 0x01010101u) << 2)), a.a[0].c, acc[0]); \
+        acc[1] = dot4((int)(((q >> 2) & 0x03030303u) | (((hm >> 1) & 0x01010101u) << 2)), a.a[1].c, acc[1]); \
+        acc[2] = dot4((int)(((q >> 4) & 0x03030303u) | (((hm >> 2) & 0x01010101u) << 2)), a.a[2].c, acc[2]); \
+        acc[3] = dot4((int)(((q >> 6) & 0x03030303u) | (((hm >> 3) & 0x01010101u) << 2)), a.a[3].c, acc[3]); }
+        MI_Q3(x) MI_Q3(y) MI_Q3(z) MI_Q3(w)
+#undef MI_Q3
+        const int isum = sc0*(acc[0] - 4*a.s[0]) + sc1*(acc[1] - 4*a.s[1]) + sc2*(acc[2] - 4*a.s[2]) + sc3*(acc[3] - 4*a.s[3]);
+        return (f16_bits_to_f32((uint16_t)(t3 >> 16))*a.d8)*(float) isum;
+    }
+};
+
 // ---- Q8_0 ---------------------------------------------------------------------------------------
 template <> struct mmvq_t<T_Q8_0> {
     static constexpr int LPB = 2, BLOCK_BYTES = 34, QK = 32, ACT = T_Q8_0;

@@ -279,6 +279,7 @@ void mul_mat_vec_q_fused(const mmvq_group * groups, int n_groups, int64_t k, con
 bool mul_mat_vec_q_fused_can_group(int type_a, int type_b) {
     if (type_a == type_b) return true;
     const int lo = type_a < type_b ? type_a : type_b, hi = type_a < type_b ? type_b : type_a;
+    if (lo == T_Q3_K) return hi == T_Q4_K || hi == T_Q5_K;      // (Q3_K_M / _L: wq, wk beside wv — streamed kernel only; Q3_K + Q6_K has no kernel)
     return (lo == T_Q4_K && (hi == T_Q5_K || hi == T_Q6_K)) || (lo == T_Q5_K && hi == T_Q6_K);
 }
 // ... and which pairs of DIFFERENT activation formats may, when every workgroup quantizes the activation itself (PRO_QUANT / PRO_NORM)

@@ -284,6 +284,59 @@ template <> struct st_unit<T_Q6_K> {
     }
 };
 
+// Q3_K: 110-byte blocks (hmask 32 B | qs 64 B | 12 scale bytes | f16 d) — a unit starts on a 2-byte boundary in the slot, as Q6_K's: a lane reads the 28 aligned
+// dwords that cover its block and realigns them with one v_alignbit each. 64 units = 7040 bytes of a 7 KiB slot: an odd lane's reads start two bytes before
+// its unit and end with it, an even lane's end two bytes past it, in the next unit (lane 63 is odd) — nothing is read past the slot's 7040 bytes.
+// Element 128 n + 32 j + l = (qs[32 n + l] >> 2 j) & 3 | bit 4 n + j of hmask[l] << 2, minus 4; group g = 8 n + 2 j + l / 16 has scale sc_g - 32
+// (quants.py:431-472). sum_g (sc_g - 32) (dot(u, a)_g - 4 bsum16_g): the second term against the sixteen 16-element sums as (h, l) bytes, as Q6_K's - 32.
+template <> struct st_unit<T_Q3_K> {
+    static constexpr int UB = 110;
+    struct wfrag { uint32_t d[28]; uint32_t sh; };
+    static __device__ __forceinline__ wfrag load(uint32_t a) {
+        wfrag w;
+        const uint32_t a4 = a & ~3u;
+        w.sh = (a & 2u)*8;
+#pragma unroll
+        for (int j = 0; j < 28; j++) w.d[j] = st_ld4(a4 + 4*j);
+        return w;
+    }
+    static __device__ __forceinline__ uint32_t dw(const wfrag & w, int i) {      // dword i of the block (the last one: its low half, d, is all that is used)
+        return __builtin_amdgcn_alignbit(w.d[i < 27 ? i + 1 : 27], w.d[i], w.sh);
+    }
+    static __device__ __forceinline__ float dot(const wfrag & w, const char * ab, float d8) {
+        // hmask (dwords 0..7) | qs (8..23) | scales (24..26) | d (27, low half)
+        uint32_t sc[4];      // the sixteen scales - 32 as signed bytes, group g in byte g % 4 of word g / 4
+        q3k_scales(dw(w, 24), dw(w, 25), dw(w, 26), sc);
+        int isum = 0;
+#pragma unroll
+        for (int n = 0; n < 2; n++) {
+            int acc[8];      // the eight 16-element groups of this half: group 8n + 2j + (t >> 2)
+#pragma unroll
+            for (int i = 0; i < 8; i++) acc[i] = 0;
+#pragma unroll
+            for (int t = 0; t < 8; t++) {
+                const uint32_t q = dw(w, 8 + 8*n + t), hm = dw(w, t) >> (4*n);
+                const int * ap = (const int *) (ab + 128*n + 4*t);
+                acc[0 + (t >> 2)] = dot4((int)(( q       & 0x03030303u) | (( hm       & 0x01010101u) << 2)), ap[0],  acc[0 + (t >> 2)]);
+                acc[2 + (t >> 2)] = dot4((int)(((q >> 2) & 0x03030303u) | (((hm >> 1) & 0x01010101u) << 2)), ap[8],  acc[2 + (t >> 2)]);
+                acc[4 + (t >> 2)] = dot4((int)(((q >> 4) & 0x03030303u) | (((hm >> 2) & 0x01010101u) << 2)), ap[16], acc[4 + (t >> 2)]);
+                acc[6 + (t >> 2)] = dot4((int)(((q >> 6) & 0x03030303u) | (((hm >> 3) & 0x01010101u) << 2)), ap[24], acc[6 + (t >> 2)]);
+            }
+#pragma unroll
+            for (int i = 0; i < 8; i++) {
+                const int s = (int)(int8_t)((sc[2*n + (i >> 2)] >> (8*(i & 3))) & 0xFF);
+                isum += __mul24(s, acc[i]);
+            }
+        }
+        const int4v H = *(const int4v *) (ab + 272), L = *(const int4v *) (ab + 288);
+        const int bs = (dot4((int) sc[0], H.x, dot4((int) sc[1], H.y, dot4((int) sc[2], H.z, dot4((int) sc[3], H.w, 0)))) << 7)
+                     +  dot4((int) sc[0], L.x, dot4((int) sc[1], L.y, dot4((int) sc[2], L.z, dot4((int) sc[3], L.w, 0))));
+        isum -= 4*bs;
+        const float d = f16_bits_to_f32((uint16_t)(dw(w, 27) & 0xFFFF));
+        return (d*d8)*(float) isum;
+    }
+};
+
 // Q8_0: 34-byte blocks of 32 weights (f16 d | 32 int8) — a unit is EIGHT of them (272 bytes = 17 chunks: odd, conflict-free, and a unit
 // starts on a 16-byte boundary). Block j's quants start 34 j + 2 bytes in: dword-aligned for odd j, two bytes off for even j (one
 // v_alignbit per dword, the shift known at compile time). The activation is the CPU path's Q8_0 (vec_dot_type of Q8_0,

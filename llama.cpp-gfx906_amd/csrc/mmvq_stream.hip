@@ -27,8 +27,9 @@ struct st_pair { int ta, tb, ub_a, ub_b; st_launch_fn glu, plain; };
 #define ST_SAME(T_)      { T_, T_, st_unit<T_>::UB, st_unit<T_>::UB, st_launch_t<T_, T_, true>, st_launch_t<T_, T_, false> }
 #define ST_MIXED(A_, B_) { A_, B_, st_unit<A_>::UB, st_unit<B_>::UB, nullptr, st_launch_t<A_, B_, false> }
 static const st_pair st_pairs[] = {
-    ST_SAME(T_Q4_K), ST_SAME(T_Q5_K), ST_SAME(T_Q6_K), ST_SAME(ST_Q8_0_B10), ST_SAME(ST_MXFP4_B10), ST_SAME(T_Q4_0), ST_SAME(T_Q8_0), ST_SAME(T_Q5_0), ST_SAME(T_Q5_1),
+    ST_SAME(T_Q4_K), ST_SAME(T_Q5_K), ST_SAME(T_Q6_K), ST_SAME(ST_Q8_0_B10), ST_SAME(ST_MXFP4_B10), ST_SAME(T_Q4_0), ST_SAME(T_Q8_0), ST_SAME(T_Q5_0), ST_SAME(T_Q5_1), ST_SAME(T_Q3_K),
     ST_MIXED(T_Q8_0, T_Q4_K), ST_MIXED(T_Q8_0, T_Q6_K), ST_MIXED(T_Q4_K, T_Q5_K), ST_MIXED(T_Q4_K, T_Q6_K), ST_MIXED(T_Q5_K, T_Q6_K),
+    ST_MIXED(T_Q3_K, T_Q4_K), ST_MIXED(T_Q3_K, T_Q5_K),      // (Q3_K_M / _L: wq and wk in Q3_K beside wv in Q4_K / Q5_K)
 };
 #undef ST_SAME
 #undef ST_MIXED

@@ -19,7 +19,7 @@ static inline size_t pad256(size_t x) { return (x + 255) & ~(size_t) 255; }
 int act_kind_for(int type_a) {
     switch (type_a) {
         case T_Q4_0: case T_Q5_0: case T_Q5_1: case T_Q8_0: case T_MXFP4: return T_Q8_0;
-        case T_Q4_K: case T_Q5_K: case T_Q6_K:  return T_Q8_K;
+        case T_Q3_K: case T_Q4_K: case T_Q5_K: case T_Q6_K:  return T_Q8_K;
         default: return -1;
     }
 }

@@ -23,10 +23,11 @@ GGML_MAX_DIMS, GGML_MAX_SRC, GGML_MAX_NAME, GGML_MAX_OP_PARAMS = 4, 10, 64, 64
 # enum ggml_type — gguf-py/gguf/constants.py:2698-2730
 F32, F16, Q4_0, Q8_0, Q4_K, Q5_K, Q6_K, Q8_K, I32, I64, BF16, MXFP4 = 0, 1, 2, 8, 12, 13, 14, 15, 26, 27, 30, 39
 Q5_0, Q5_1 = 6, 7
+Q3_K = 11
 TYPE_NP = {F32: np.float32, F16: np.float16, I32: np.int32, I64: np.int64}
 # (block size, type size) — gguf-py/gguf/constants.py:2839-2872
 QUANT_SIZES = {F32: (1, 4), F16: (1, 2), BF16: (1, 2), I32: (1, 4), I64: (1, 8), Q4_0: (32, 18), Q5_0: (32, 22), Q5_1: (32, 24), Q8_0: (32, 34),
-               Q4_K: (256, 144), Q5_K: (256, 176), Q6_K: (256, 210), MXFP4: (32, 17)}
+               Q3_K: (256, 110), Q4_K: (256, 144), Q5_K: (256, 176), Q6_K: (256, 210), MXFP4: (32, 17)}
 
 GGML_STATUS_SUCCESS = 0
 GGML_ROPE_TYPE_NEOX = 2
