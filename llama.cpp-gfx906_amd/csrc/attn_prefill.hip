@@ -361,7 +361,7 @@ void attn_prefill(const attn_call & c) {
     if (c.n_stream > 1) { a.q_nb3 = c.q_nb3; a.k_nb3 = c.k_nb3; a.v_nb3 = c.v_nb3; a.m_nb3 = c.m_nb3; a.dst_nb3 = c.dst_nb3; }
     attn_set_softmax(a, c);
     // the (hsk, hsv) pairs of attn_fa_head_sizes x the mask's kind (0 = none, 1 = f32, 2 = f16) x the plan's ks, one instantiation each
-    attn_dispatch_sizes(c.hsk, c.hsv, [&](auto hk, auto hv) { attn_dispatch_int<0, 1, 2>(c.mask_type == T_NONE ? 0 : c.mask_type == T_F16 ? 2 : 1, [&](auto mk) { attn_dispatch_int<1, 2, 4>(pl.ks, [&](auto ks) {
+    attn_dispatch_sizes(c.hsk, c.hsv, [&](auto hk, auto hv) { dispatch_int<0, 1, 2>(c.mask_type == T_NONE ? 0 : c.mask_type == T_F16 ? 2 : 1, [&](auto mk) { dispatch_int<1, 2, 4>(pl.ks, [&](auto ks) {
         constexpr int HK = decltype(hk)::value, HV = decltype(hv)::value, MK = decltype(mk)::value, KS = decltype(ks)::value, NW = HK > 128 ? 4 : APF_NW;
         if (c.v_trans) apf_launch<HK, true, MK, KS, HV, NW>(a, pl, c.stream);
         else if constexpr (HK == HV && (HK == 64 || HK == 128)) apf_launch<HK, false, MK, KS, HV, NW>(a, pl, c.stream);
@@ -411,7 +411,7 @@ void kv_to_f16(int type, const void * src, size_t nb1, size_t nb2, size_t nb3, i
     if (hd % 8 || hd < 8 || hd > 256 || ((type == T_Q8_0 || type == T_Q4_0) && hd % 32) || n_kv % 8 || n_kv < 8 || n_heads > 65535) { fprintf(stderr, "kv_to_f16: unsupported shape (hd %lld, n_kv %lld)\n", (long long) hd, (long long) n_kv); abort(); }
     const kvc_args a = { (const char *) src, nb1, nb2, nb3, (int) hd, (int) n_kv, (int) n_head_kv, (int) n_heads, dst };
     const long long tot = (long long) n_heads*n_kv*(hd/8);
-    if (!attn_dispatch_int<T_F16, T_BF16, T_Q8_0, T_Q4_0>(type, [&](auto ty) {
+    if (!dispatch_int<T_F16, T_BF16, T_Q8_0, T_Q4_0>(type, [&](auto ty) {
             constexpr int TY = decltype(ty)::value;
             if (transpose) hipLaunchKernelGGL((k_kv_trans_f16<TY>), dim3((unsigned)((n_kv + 63)/64), (unsigned) n_heads, (unsigned)((hd + 127)/128)), dim3(256), 0, stream, a);
             else           hipLaunchKernelGGL((k_kv_rows_f16<TY>), dim3((unsigned)((tot + 255)/256)), dim3(256), 0, stream, a);

@@ -572,7 +572,7 @@ static int try_fused_mmv(mi_backend_ctx * c, struct ggml_cgraph * g, int i, int 
         }
         rope_l = *rope; rope_l.table = c->rope_tab; rope = &rope_l;
     }
-    if (!mul_mat_vec_q_fused_takes(grp, nc, K, in, rope)) return -1;      // (Q5_0 / Q5_1 / Q3_K groups the streamed kernel declines: node by node)
+    if (!mul_mat_vec_q_fused_takes(grp, nc, K, in, rope)) return -1;      // (a format without a register-ring kernel — mmvq_fused.hip: fused_pairs — in a launch the streamed kernel declines: node by node)
     if (c->pass.pp.active && in.mode == PRO_NORM && (const void *) in.x == (const void *) c->pass.pp.x_out && K == c->pass.pp.m) {
         // the norm's input is the MoE combine left pending: this launch evaluates it in its prologue (and stores the sum). EVERY workgroup's prologue reads the
         // residual, the experts' outputs, the router's probabilities and the ids while other workgroups already store their rows — and by graph order all four are

@@ -1,10 +1,11 @@
 // blocks.h — GGUF block formats as the backend sees them in HBM (raw GGUF bytes,
 // unmodified: src/llama-model-loader.cpp:1060 uploads them as-is).
 // Layouts: gguf-py/gguf/quants.py (class per type, cited below); sizes:
-// gguf-py/gguf/constants.py:2839-2872. Shared by host and device code.
+// gguf-py/gguf/constants.py:2839-2872 — and the list of weight formats built on them. Shared by host and device code.
 #pragma once
 
 #include <stdint.h>
+#include <type_traits>
 
 #define MI_QK_K 256
 #define MI_K_SCALE_SIZE 12
@@ -32,12 +33,34 @@ struct block_q6_K { uint8_t ql[MI_QK_K/2]; uint8_t qh[MI_QK_K/4]; int8_t scales[
 struct block_mxfp4 { uint8_t e; uint8_t qs[16]; };
 #pragma pack(pop)
 
-static_assert(sizeof(block_q4_0)  == 18,  "Q4_0 block size (constants.py:2842)");
-static_assert(sizeof(block_q5_0)  == 22,  "Q5_0 block size (constants.py:2844)");
-static_assert(sizeof(block_q5_1)  == 24,  "Q5_1 block size (constants.py:2845)");
-static_assert(sizeof(block_q8_0)  == 34,  "Q8_0 block size (constants.py:2846)");
-static_assert(sizeof(block_q3_K)  == 110, "Q3_K block size (constants.py:2849)");
-static_assert(sizeof(block_q4_K)  == 144, "Q4_K block size (constants.py:2850)");
-static_assert(sizeof(block_q5_K)  == 176, "Q5_K block size (constants.py:2851)");
-static_assert(sizeof(block_q6_K)  == 210, "Q6_K block size (constants.py:2852)");
-static_assert(sizeof(block_mxfp4) == 17,  "MXFP4 block size (constants.py:2871)");
+namespace mi355x {
+// THE list of weight formats MUL_MAT(_ID) takes: X(name, ggml_type id, block struct, elements per block, bytes per block, activation format). Ids: constants.py:2698-2730;
+// sizes: constants.py:2839-2872; activation format = the CPU path's vec_dot_type. Every plain fact about a format is generated from here — the T_<name> constants, the
+// size asserts, weight_format_of(), weight_format_dispatch(); what stays per format is code shaped for one kernel (DESIGN.md "Adding a weight format").
+#define MI_WEIGHT_FORMATS(X) \
+    X(Q4_0,  2,  block_q4_0,  32,  18,  Q8_0) X(Q5_0,  6,  block_q5_0,  32,  22,  Q8_0) X(Q5_1,  7,  block_q5_1,  32,  24,  Q8_0) \
+    X(Q8_0,  8,  block_q8_0,  32,  34,  Q8_0) X(Q3_K,  11, block_q3_K,  256, 110, Q8_K) X(Q4_K,  12, block_q4_K,  256, 144, Q8_K) \
+    X(Q5_K,  13, block_q5_K,  256, 176, Q8_K) X(Q6_K,  14, block_q6_K,  256, 210, Q8_K) X(MXFP4, 39, block_mxfp4, 32,  17,  Q8_0)
+#define MI_X(N_, ID_, B_, QK_, BYTES_, A_) T_##N_ = ID_,
+enum : int { MI_WEIGHT_FORMATS(MI_X) T_Q8_K = 15 };      // (Q8_K: the K-quants' activation format, never a weight)
+#undef MI_X
+// a row of the list by run-time or compile-time type, in host and device code; qk == 0: the type is not in the list
+struct weight_format { int qk, bytes, act; };
+constexpr weight_format weight_format_of(int type) {
+    switch (type) {
+#define MI_X(N_, ID_, B_, QK_, BYTES_, A_) case ID_: static_assert(sizeof(B_) == BYTES_, #N_ " block size"); return { QK_, BYTES_, T_##A_ };
+        MI_WEIGHT_FORMATS(MI_X)
+#undef MI_X
+        default: return { 0, 0, -1 };
+    }
+}
+// a run-time weight type as a compile-time tag: calls f(std::integral_constant<int, type>{}); false: the type is not in the list (f was not called)
+template <typename F> static inline bool weight_format_dispatch(int type, F && f) {
+    switch (type) {
+#define MI_X(N_, ID_, B_, QK_, BYTES_, A_) case ID_: f(std::integral_constant<int, ID_>{}); return true;
+        MI_WEIGHT_FORMATS(MI_X)
+#undef MI_X
+        default: return false;
+    }
+}
+} // namespace mi355x

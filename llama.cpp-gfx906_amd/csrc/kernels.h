@@ -13,17 +13,15 @@
 #include <stdint.h>
 #include <type_traits>
 
+#include "blocks.h"
 #include "env_switch.h"
 
 namespace mi355x {
 
-// ggml_type ids used on the path (gguf-py/gguf/constants.py:2698-2730)
-enum : int {
-    T_F32 = 0, T_F16 = 1, T_Q4_0 = 2, T_Q5_0 = 6, T_Q5_1 = 7, T_Q8_0 = 8, T_Q3_K = 11, T_Q4_K = 12, T_Q5_K = 13, T_Q6_K = 14, T_Q8_K = 15,
-    T_I32 = 26, T_I64 = 27, T_BF16 = 30, T_MXFP4 = 39,
-};
+// ggml_type ids used on the path (gguf-py/gguf/constants.py:2698-2730); the weight formats' ids and T_Q8_K come from the list in blocks.h
+enum : int { T_F32 = 0, T_F16 = 1, T_I32 = 26, T_I64 = 27, T_BF16 = 30 };
 
-// ---- activation quantisation (the CPU path's vec_dot_type: Q8_0 for Q4_0/Q5_0/Q5_1/Q8_0/MXFP4, Q8_K for K-quants)
+// ---- activation quantisation (the CPU path's vec_dot_type, the list's last column: Q8_0 for the 32-element formats, Q8_K for the K-quants)
 // Device layout (SoA, internal): for a [k, n] activation
 //   qs    : int8  [n][k]
 //   d     : float [n][k/32]   (Q8_0: value of the f16-rounded scale)  | float [n][k/256] (Q8_K)
@@ -39,7 +37,7 @@ struct act_q8 {
 
 size_t act_q8_bytes(int kind, int64_t k, int64_t n);            // scratch bytes needed
 act_q8 act_q8_carve(void * scratch, int kind, int64_t k, int64_t n);
-int    act_kind_for(int type_a);                                   // T_Q8_0 / T_Q8_K / -1
+int    act_kind_for(int type_a);                                   // T_Q8_0 / T_Q8_K / -1: the list's activation format
 
 // x: f32, rows of k contiguous floats; row r (< q.n) lives at
 //   x + (r % n_inner)*stride_inner + (r / n_inner)*stride_outer      (bytes)
@@ -48,7 +46,7 @@ void quantize_act(const float * x, int64_t n_inner, size_t stride_inner, size_t 
 
 // ---- quantized mat-vec (decode, n <= MMVQ_MAX_N): dst[col*dst_stride + row] = W[row,:] . x[col,:]
 constexpr int MMVQ_MAX_N = 8;
-bool mul_mat_vec_q_supported(int type_a);
+bool mul_mat_vec_q_supported(int type_a);      // = the type is in the list (blocks.h)
 void mul_mat_vec_q(int type_a, const void * W, size_t w_row_stride, int64_t m, int64_t k,
                    const act_q8 & act, int64_t n, float * dst, size_t dst_col_stride_bytes, hipStream_t stream);
 
@@ -270,7 +268,7 @@ template <typename A> static inline void attn_set_softmax(A & a, const attn_call
     a.n_head_log2 = 1; while (2*a.n_head_log2 <= (int) c.n_head) a.n_head_log2 *= 2;
     a.m0 = powf(2.0f, -c.max_bias/(float) a.n_head_log2); a.m1 = powf(2.0f, -(c.max_bias/2.0f)/(float) a.n_head_log2);
 }
-// the instantiations: f(K, V) with the matching pair as two std::integral_constant (as mmq_dispatch_type, mmq.hip); false: no such pair
+// the instantiations: f(K, V) with the matching pair as two std::integral_constant (as weight_format_dispatch, blocks.h); false: no such pair
 template <int A, int B, typename F> static inline bool attn_pair_is(int64_t a, int64_t b, F & f) { return a == A && b == B && (f(std::integral_constant<int, A>{}, std::integral_constant<int, B>{}), true); }
 template <typename F> static inline bool attn_dispatch_sizes(int64_t hsk, int64_t hsv, F && f) {      // the pairs of attn_fa_head_sizes
     return attn_pair_is<64, 64>(hsk, hsv, f) || attn_pair_is<80, 80>(hsk, hsv, f) || attn_pair_is<96, 96>(hsk, hsv, f) || attn_pair_is<128, 128>(hsk, hsv, f) ||
@@ -280,7 +278,8 @@ template <typename F> static inline bool attn_dispatch_types(int k_type, int v_t
     return attn_pair_is<T_F16, T_F16>(k_type, v_type, f) || attn_pair_is<T_Q8_0, T_Q8_0>(k_type, v_type, f) || attn_pair_is<T_Q4_0, T_Q4_0>(k_type, v_type, f) ||
            attn_pair_is<T_BF16, T_BF16>(k_type, v_type, f) || attn_pair_is<T_Q8_0, T_F16>(k_type, v_type, f) || attn_pair_is<T_Q8_0, T_Q4_0>(k_type, v_type, f);
 }
-template <int... Vs, typename F> static inline bool attn_dispatch_int(int v, F && f) { return ((v == Vs && (f(std::integral_constant<int, Vs>{}), true)) || ...); }
+// a run-time int as a compile-time tag: f(std::integral_constant<int, v>{}) when v is one of Vs; false: it is not
+template <int... Vs, typename F> static inline bool dispatch_int(int v, F && f) { return ((v == Vs && (f(std::integral_constant<int, Vs>{}), true)) || ...); }
 
 // the persistent kernels run one workgroup per CU: the current device's CU count, asked for once (mmvq_fused.hip)
 int device_cu_count();
@@ -351,7 +350,7 @@ void mul_mat_vec_q_fused(const mmvq_group * groups, int n_groups, int64_t k, con
 bool mul_mat_vec_q_stream_enabled(void);       // GGML_MI355X_STREAM (default 1)
 bool mul_mat_vec_q_stream_takes(const mmvq_group * groups, int n_groups, int64_t k, const mmvq_input & in, const mmvq_rope * rope);     // = the launch's plan is ok (mmvq_stream.h: st_plan)
 // may this grouped launch be handed to mul_mat_vec_q_fused at all: every group's format has a register-ring kernel (mmvq_fused_<format>.hip), or the streamed kernel
-// takes the launch as it stands. Q5_0 / Q5_1 / Q3_K have no register-ring kernels: a matcher asks this before it emits and runs the nodes one by one on false
+// takes the launch as it stands. Not every format of the list has a register-ring kernel (mmvq_fused.hip: fused_pairs): a matcher asks this before it emits and runs the nodes one by one on false
 bool mul_mat_vec_q_fused_takes(const mmvq_group * groups, int n_groups, int64_t k, const mmvq_input & in, const mmvq_rope * rope);
 bool mul_mat_vec_q_fused_fin_supported(int64_t m, int64_t k_in);   // may a GLU launch with m output rows carry an mmvq_fin
 

@@ -80,7 +80,7 @@ static __device__ __forceinline__ uint32_t raw_word(const raw32 & r, int i) {   
 
 // Q4_0 — quants.py:241-251: element j < 16 = low nibble of byte j, element 16 + j = high nibble
 template <> __device__ __forceinline__ raw32 load_raw32<T_Q4_0>(const char * row, int c32) {
-    raw32 r; const char * b = row + (size_t) c32*18; r.s = ld_u16(b); r.v[0] = ld_b128(b + 2); return r;
+    raw32 r; const char * b = row + (size_t) c32*weight_format_of(T_Q4_0).bytes; r.s = ld_u16(b); r.v[0] = ld_b128(b + 2); return r;
 }
 template <> __device__ __forceinline__ dq_head decode_head<T_Q4_0>(const raw32 & r, int) { return { f16_bits_to_f32((uint16_t) r.s), 0.0f }; }
 template <> __device__ __forceinline__ void decode4<T_Q4_0>(const raw32 & r, const dq_head & h, int, int ws, int wi, float (&o)[4]) {
@@ -94,7 +94,7 @@ static __device__ __forceinline__ uint32_t q5_word(const raw32 & r, int ws, int 
     return ((raw_word(r, ws & 3) >> (4*(wi >> 2))) & 0x0F0F0F0Fu) | ((__umul24(hb, 0x00204081u) & 0x01010101u) << 4);
 }
 template <> __device__ __forceinline__ raw32 load_raw32<T_Q5_0>(const char * row, int c32) {
-    raw32 r; const char * b = row + (size_t) c32*22; r.s = ld_u16(b); r.v[1].x = (int) ld_u32(b + 2); r.v[0] = ld_b128(b + 6); return r;
+    raw32 r; const char * b = row + (size_t) c32*weight_format_of(T_Q5_0).bytes; r.s = ld_u16(b); r.v[1].x = (int) ld_u32(b + 2); r.v[0] = ld_b128(b + 6); return r;
 }
 template <> __device__ __forceinline__ dq_head decode_head<T_Q5_0>(const raw32 & r, int) { return { f16_bits_to_f32((uint16_t) r.s), 0.0f }; }
 template <> __device__ __forceinline__ void decode4<T_Q5_0>(const raw32 & r, const dq_head & h, int, int ws, int wi, float (&o)[4]) {
@@ -103,7 +103,7 @@ template <> __device__ __forceinline__ void decode4<T_Q5_0>(const raw32 & r, con
     for (int b = 0; b < 4; b++) o[b] = (float)((int)((q5 >> (8*b)) & 0xFF) - 16)*h.a;
 }
 template <> __device__ __forceinline__ raw32 load_raw32<T_Q5_1>(const char * row, int c32) {
-    raw32 r; const char * b = row + (size_t) c32*24; const int2v h = ld_b64(b); r.s = (uint32_t) h.x; r.v[1].x = h.y; r.v[0] = ld_b128(b + 8); return r;
+    raw32 r; const char * b = row + (size_t) c32*weight_format_of(T_Q5_1).bytes; const int2v h = ld_b64(b); r.s = (uint32_t) h.x; r.v[1].x = h.y; r.v[0] = ld_b128(b + 8); return r;
 }
 template <> __device__ __forceinline__ dq_head decode_head<T_Q5_1>(const raw32 & r, int) { return { f16_bits_to_f32((uint16_t)(r.s & 0xFFFF)), f16_bits_to_f32((uint16_t)(r.s >> 16)) }; }
 template <> __device__ __forceinline__ void decode4<T_Q5_1>(const raw32 & r, const dq_head & h, int, int ws, int wi, float (&o)[4]) {
@@ -113,7 +113,7 @@ template <> __device__ __forceinline__ void decode4<T_Q5_1>(const raw32 & r, con
 }
 // Q8_0 — quants.py:396-401
 template <> __device__ __forceinline__ raw32 load_raw32<T_Q8_0>(const char * row, int c32) {
-    raw32 r; const char * b = row + (size_t) c32*34; r.s = ld_u16(b); r.v[0] = ld_b128(b + 2); r.v[1] = ld_b128(b + 18); return r;
+    raw32 r; const char * b = row + (size_t) c32*weight_format_of(T_Q8_0).bytes; r.s = ld_u16(b); r.v[0] = ld_b128(b + 2); r.v[1] = ld_b128(b + 18); return r;
 }
 template <> __device__ __forceinline__ dq_head decode_head<T_Q8_0>(const raw32 & r, int) { return { f16_bits_to_f32((uint16_t) r.s), 0.0f }; }
 template <> __device__ __forceinline__ void decode4<T_Q8_0>(const raw32 & r, const dq_head & h, int, int ws, int, float (&o)[4]) {
@@ -123,7 +123,7 @@ template <> __device__ __forceinline__ void decode4<T_Q8_0>(const raw32 & r, con
 }
 // MXFP4 — quants.py:656-700: nibble order as Q4_0; kvalues (quants.py:659): magnitude by the low 3 bits, sign by bit 3
 template <> __device__ __forceinline__ raw32 load_raw32<T_MXFP4>(const char * row, int c32) {
-    raw32 r; const char * b = row + (size_t) c32*17; r.s = *(const uint8_t *) b; r.v[0] = ld_b128(b + 1); return r;
+    raw32 r; const char * b = row + (size_t) c32*weight_format_of(T_MXFP4).bytes; r.s = *(const uint8_t *) b; r.v[0] = ld_b128(b + 1); return r;
 }
 template <> __device__ __forceinline__ dq_head decode_head<T_MXFP4>(const raw32 & r, int) { return { e8m0_to_f32_half(r.s), 0.0f }; }
 template <> __device__ __forceinline__ void decode4<T_MXFP4>(const raw32 & r, const dq_head & h, int, int ws, int wi, float (&o)[4]) {
@@ -162,7 +162,7 @@ static __device__ __forceinline__ uint32_t q3k_scale_pairs(const char * b, int c
     return (uint32_t) ld_u16(b + 96 + 2*(c & 3)) | ((uint32_t) ld_u16(b + 104 + 2*(c & 1)) << 16);
 }
 template <> __device__ __forceinline__ raw32 load_raw32<T_Q3_K>(const char * row, int c32) {
-    raw32 r; const int c = c32 & 7, n = c >> 2; const char * b = row + (size_t)(c32 >> 3)*110;   // 2-byte aligned only
+    raw32 r; const int c = c32 & 7, n = c >> 2; const char * b = row + (size_t)(c32 >> 3)*weight_format_of(T_Q3_K).bytes;   // 2-byte aligned only
     r.v[0] = ld_b128(b + 32 + 32*n); r.v[1] = ld_b128(b + 32 + 32*n + 16); r.v[2] = ld_b128(b); r.v[3] = ld_b128(b + 16);
     r.v[4].x = (int) q3k_scale_pairs(b, c); r.s = ld_u16(b + 108);
     return r;
@@ -184,7 +184,7 @@ template <> __device__ __forceinline__ void decode4<T_Q3_K>(const raw32 & r, con
 }
 // Q4_K — quants.py:504-522
 template <> __device__ __forceinline__ raw32 load_raw32<T_Q4_K>(const char * row, int c32) {
-    raw32 r; const int sb = c32 & 7; const char * b = row + (size_t)(c32 >> 3)*144;
+    raw32 r; const int sb = c32 & 7; const char * b = row + (size_t)(c32 >> 3)*weight_format_of(T_Q4_K).bytes;
     r.v[0] = *(const int4v *) b; r.v[1] = *(const int4v *) (b + 16 + 32*(sb >> 1)); r.v[2] = *(const int4v *) (b + 32 + 32*(sb >> 1)); r.s = 0; return r;
 }
 static __device__ __forceinline__ dq_head k45_head(const raw32 & r, int c32) {
@@ -202,7 +202,7 @@ template <> __device__ __forceinline__ void decode4<T_Q4_K>(const raw32 & r, con
 }
 // Q5_K — quants.py:527-549
 template <> __device__ __forceinline__ raw32 load_raw32<T_Q5_K>(const char * row, int c32) {
-    raw32 r; const int sb = c32 & 7; const char * b = row + (size_t)(c32 >> 3)*176;
+    raw32 r; const int sb = c32 & 7; const char * b = row + (size_t)(c32 >> 3)*weight_format_of(T_Q5_K).bytes;
     r.v[0] = *(const int4v *) b; r.v[1] = *(const int4v *) (b + 16); r.v[2] = *(const int4v *) (b + 32);
     r.v[3] = *(const int4v *) (b + 48 + 32*(sb >> 1)); r.v[4] = *(const int4v *) (b + 64 + 32*(sb >> 1)); r.s = 0; return r;
 }
@@ -215,7 +215,7 @@ template <> __device__ __forceinline__ void decode4<T_Q5_K>(const raw32 & r, con
 }
 // Q6_K — quants.py:554-572. chunk c of a 256-superblock: half n = c>>2, quarter pq = c&3: elements 128n + 32pq + l
 template <> __device__ __forceinline__ raw32 load_raw32<T_Q6_K>(const char * row, int c32) {
-    raw32 r; const int c = c32 & 7, n = c >> 2, pq = c & 3; const char * b = row + (size_t)(c32 >> 3)*210;   // 2-byte aligned only
+    raw32 r; const int c = c32 & 7, n = c >> 2, pq = c & 3; const char * b = row + (size_t)(c32 >> 3)*weight_format_of(T_Q6_K).bytes;   // 2-byte aligned only
     const char * ql = b + 64*n + 32*(pq & 1);
     r.v[0] = ld_b128(ql); r.v[1] = ld_b128(ql + 16); r.v[2] = ld_b128(b + 128 + 32*n); r.v[3] = ld_b128(b + 128 + 32*n + 16);
     r.s = (uint32_t) ld_u16(b + 208) | ((uint32_t) ld_u16(b + 192 + 8*n + 2*pq) << 16);
@@ -529,40 +529,40 @@ __global__ void __launch_bounds__(BN*2) __attribute__((amdgpu_waves_per_eu(2, 2)
 // Quarter-chunk loads: thread -> (row, 32-chunk, quarter q): pieces 2q, 2q + 1; their words land in word slots 0, 1 of each vector.
 template <int TYPE> static __device__ __forceinline__ raw32 load_raw8(const char * row, int c32, int q);
 template <> __device__ __forceinline__ raw32 load_raw8<T_Q4_0>(const char * row, int c32, int q) {
-    raw32 r; const char * b = row + (size_t) c32*18; r.s = ld_u16(b); const int2v t = ld_b64(b + 2 + 8*(q & 1)); r.v[0].x = t.x; r.v[0].y = t.y; return r;
+    raw32 r; const char * b = row + (size_t) c32*weight_format_of(T_Q4_0).bytes; r.s = ld_u16(b); const int2v t = ld_b64(b + 2 + 8*(q & 1)); r.v[0].x = t.x; r.v[0].y = t.y; return r;
 }
 template <> __device__ __forceinline__ raw32 load_raw8<T_Q5_0>(const char * row, int c32, int q) {
-    raw32 r; const char * b = row + (size_t) c32*22; r.s = ld_u16(b); r.v[1].x = (int) ld_u32(b + 2); const int2v t = ld_b64(b + 6 + 8*(q & 1)); r.v[0].x = t.x; r.v[0].y = t.y; return r;
+    raw32 r; const char * b = row + (size_t) c32*weight_format_of(T_Q5_0).bytes; r.s = ld_u16(b); r.v[1].x = (int) ld_u32(b + 2); const int2v t = ld_b64(b + 6 + 8*(q & 1)); r.v[0].x = t.x; r.v[0].y = t.y; return r;
 }
 template <> __device__ __forceinline__ raw32 load_raw8<T_Q5_1>(const char * row, int c32, int q) {
-    raw32 r; const char * b = row + (size_t) c32*24; const int2v h = ld_b64(b), t = ld_b64(b + 8 + 8*(q & 1)); r.s = (uint32_t) h.x; r.v[1].x = h.y; r.v[0].x = t.x; r.v[0].y = t.y; return r;
+    raw32 r; const char * b = row + (size_t) c32*weight_format_of(T_Q5_1).bytes; const int2v h = ld_b64(b), t = ld_b64(b + 8 + 8*(q & 1)); r.s = (uint32_t) h.x; r.v[1].x = h.y; r.v[0].x = t.x; r.v[0].y = t.y; return r;
 }
 template <> __device__ __forceinline__ raw32 load_raw8<T_MXFP4>(const char * row, int c32, int q) {
-    raw32 r; const char * b = row + (size_t) c32*17; r.s = *(const uint8_t *) b; const int2v t = ld_b64(b + 1 + 8*(q & 1)); r.v[0].x = t.x; r.v[0].y = t.y; return r;
+    raw32 r; const char * b = row + (size_t) c32*weight_format_of(T_MXFP4).bytes; r.s = *(const uint8_t *) b; const int2v t = ld_b64(b + 1 + 8*(q & 1)); r.v[0].x = t.x; r.v[0].y = t.y; return r;
 }
 template <> __device__ __forceinline__ raw32 load_raw8<T_Q8_0>(const char * row, int c32, int q) {
-    raw32 r; const char * b = row + (size_t) c32*34; r.s = ld_u16(b); const int2v t = ld_b64(b + 2 + 8*q); r.v[0].x = t.x; r.v[0].y = t.y; return r;
+    raw32 r; const char * b = row + (size_t) c32*weight_format_of(T_Q8_0).bytes; r.s = ld_u16(b); const int2v t = ld_b64(b + 2 + 8*q); r.v[0].x = t.x; r.v[0].y = t.y; return r;
 }
 template <> __device__ __forceinline__ raw32 load_raw8<T_Q4_K>(const char * row, int c32, int q) {
-    raw32 r; const int sb = c32 & 7; const char * b = row + (size_t)(c32 >> 3)*144;
+    raw32 r; const int sb = c32 & 7; const char * b = row + (size_t)(c32 >> 3)*weight_format_of(T_Q4_K).bytes;
     r.v[0] = *(const int4v *) b; r.s = 0;
     const int2v t = *(const int2v *) (b + 16 + 32*(sb >> 1) + 8*q); r.v[1].x = t.x; r.v[1].y = t.y; return r;
 }
 template <> __device__ __forceinline__ raw32 load_raw8<T_Q5_K>(const char * row, int c32, int q) {
-    raw32 r; const int sb = c32 & 7; const char * b = row + (size_t)(c32 >> 3)*176;
+    raw32 r; const int sb = c32 & 7; const char * b = row + (size_t)(c32 >> 3)*weight_format_of(T_Q5_K).bytes;
     r.v[0] = *(const int4v *) b; r.s = 0;
     const int2v h = *(const int2v *) (b + 16 + 8*q), t = *(const int2v *) (b + 48 + 32*(sb >> 1) + 8*q);
     r.v[1].x = h.x; r.v[1].y = h.y; r.v[3].x = t.x; r.v[3].y = t.y; return r;
 }
 template <> __device__ __forceinline__ raw32 load_raw8<T_Q3_K>(const char * row, int c32, int q) {
-    raw32 r; const int c = c32 & 7, n = c >> 2; const char * b = row + (size_t)(c32 >> 3)*110;   // 2-byte aligned only
+    raw32 r; const int c = c32 & 7, n = c >> 2; const char * b = row + (size_t)(c32 >> 3)*weight_format_of(T_Q3_K).bytes;   // 2-byte aligned only
     const int2v l = ld_b64(b + 32 + 32*n + 8*q), h = ld_b64(b + 8*q);
     r.v[0].x = l.x; r.v[0].y = l.y; r.v[2].x = h.x; r.v[2].y = h.y;
     r.v[4].x = (int) q3k_scale_pairs(b, c); r.s = ld_u16(b + 108);
     return r;
 }
 template <> __device__ __forceinline__ raw32 load_raw8<T_Q6_K>(const char * row, int c32, int q) {
-    raw32 r; const int c = c32 & 7, n = c >> 2, pq = c & 3; const char * b = row + (size_t)(c32 >> 3)*210;   // 2-byte aligned only
+    raw32 r; const int c = c32 & 7, n = c >> 2, pq = c & 3; const char * b = row + (size_t)(c32 >> 3)*weight_format_of(T_Q6_K).bytes;   // 2-byte aligned only
     const int2v l = ld_b64(b + 64*n + 32*(pq & 1) + 8*q), h = ld_b64(b + 128 + 32*n + 8*q);
     r.v[0].x = l.x; r.v[0].y = l.y; r.v[2].x = h.x; r.v[2].y = h.y;
     r.s = (uint32_t) ld_u16(b + 208) | ((uint32_t) ld_u16(b + 192 + 8*n + 2*pq) << 16);
@@ -1065,20 +1065,9 @@ template <auto KERNEL> static void mmq_launch(dim3 grid, int block, size_t lds_b
     MI_LDS_LIMIT_OR_DIE(lds_bytes, KERNEL);
     hipLaunchKernelGGL(KERNEL, grid, dim3(block), lds_bytes, stream, a);
 }
-// a run-time block format as a compile-time tag: calls f(std::integral_constant<int, type>); any other type aborts with the caller's name
+// weight_format_dispatch (blocks.h) for the launchers here: a type that is not in the list aborts with the caller's name
 template <typename F> static void mmq_dispatch_type(int type, const char * who, F && f) {
-    switch (type) {
-        case T_Q4_0:  f(std::integral_constant<int, T_Q4_0>{});  break;
-        case T_Q5_0:  f(std::integral_constant<int, T_Q5_0>{});  break;
-        case T_Q5_1:  f(std::integral_constant<int, T_Q5_1>{});  break;
-        case T_Q8_0:  f(std::integral_constant<int, T_Q8_0>{});  break;
-        case T_Q3_K:  f(std::integral_constant<int, T_Q3_K>{});  break;
-        case T_Q4_K:  f(std::integral_constant<int, T_Q4_K>{});  break;
-        case T_Q5_K:  f(std::integral_constant<int, T_Q5_K>{});  break;
-        case T_Q6_K:  f(std::integral_constant<int, T_Q6_K>{});  break;
-        case T_MXFP4: f(std::integral_constant<int, T_MXFP4>{}); break;
-        default: fprintf(stderr, "%s: unsupported type %d\n", who, type); abort();
-    }
+    if (!weight_format_dispatch(type, f)) { fprintf(stderr, "%s: unsupported type %d\n", who, type); abort(); }
 }
 // the f32 -> bf16 (F16: f16) activation copy: rows x + i1*nb1 + i2*nb2 + i3*nb3 (n x ne2 x ne3 of them, k floats each) -> dense rows of kp(k) elements at xb
 template <bool F16> static void mmq_act_to_16(const void * x, size_t nb1, size_t nb2, size_t nb3, int64_t k, int64_t n, int64_t ne2, int64_t ne3, uint16_t * xb, hipStream_t stream) {

@@ -236,12 +236,7 @@ static bool launch_mmvq_cols(const mmvq_args & a, int act_kind, hipStream_t stre
 // ------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------
-bool mul_mat_vec_q_supported(int type_a) {
-    switch (type_a) {
-        case T_Q4_0: case T_Q5_0: case T_Q5_1: case T_Q8_0: case T_Q3_K: case T_Q4_K: case T_Q5_K: case T_Q6_K: case T_MXFP4: return true;
-        default: return false;
-    }
-}
+bool mul_mat_vec_q_supported(int type_a) { return weight_format_of(type_a).qk != 0; }
 
 template <int TYPE, int NCOLS, bool IDS>
 static void launch_mmvq_n(const mmvq_args & a, int act_kind, int64_t n_pairs, hipStream_t stream) {
@@ -268,32 +263,15 @@ static void launch_mmvq_n(const mmvq_args & a, int act_kind, int64_t n_pairs, hi
 
 template <int TYPE, bool IDS>
 static void launch_mmvq_t(const mmvq_args & a, int act_kind, int64_t n, int64_t n_pairs, hipStream_t stream) {
-    switch (n) {
-        case 1: launch_mmvq_n<TYPE, 1, IDS>(a, act_kind, n_pairs, stream); break;
-        case 2: launch_mmvq_n<TYPE, 2, IDS>(a, act_kind, n_pairs, stream); break;
-        case 3: launch_mmvq_n<TYPE, 3, IDS>(a, act_kind, n_pairs, stream); break;
-        case 4: launch_mmvq_n<TYPE, 4, IDS>(a, act_kind, n_pairs, stream); break;
-        case 5: launch_mmvq_n<TYPE, 5, IDS>(a, act_kind, n_pairs, stream); break;
-        case 6: launch_mmvq_n<TYPE, 6, IDS>(a, act_kind, n_pairs, stream); break;
-        case 7: launch_mmvq_n<TYPE, 7, IDS>(a, act_kind, n_pairs, stream); break;
-        case 8: launch_mmvq_n<TYPE, 8, IDS>(a, act_kind, n_pairs, stream); break;
-        default: fprintf(stderr, "mmvq: n=%lld out of range\n", (long long) n); abort();
+    if (n > MMVQ_MAX_N || !dispatch_int<1, 2, 3, 4, 5, 6, 7, 8>((int) n, [&](auto nc) { launch_mmvq_n<TYPE, decltype(nc)::value, IDS>(a, act_kind, n_pairs, stream); })) {
+        fprintf(stderr, "mmvq: n=%lld out of range\n", (long long) n); abort();
     }
 }
 
 template <bool IDS>
 static void launch_mmvq(int type_a, const mmvq_args & a, int act_kind, int64_t n, int64_t n_pairs, hipStream_t stream) {
-    switch (type_a) {
-        case T_Q4_0:  launch_mmvq_t<T_Q4_0,  IDS>(a, act_kind, n, n_pairs, stream); break;
-        case T_Q5_0:  launch_mmvq_t<T_Q5_0,  IDS>(a, act_kind, n, n_pairs, stream); break;
-        case T_Q5_1:  launch_mmvq_t<T_Q5_1,  IDS>(a, act_kind, n, n_pairs, stream); break;
-        case T_Q8_0:  launch_mmvq_t<T_Q8_0,  IDS>(a, act_kind, n, n_pairs, stream); break;
-        case T_Q3_K:  launch_mmvq_t<T_Q3_K,  IDS>(a, act_kind, n, n_pairs, stream); break;
-        case T_Q4_K:  launch_mmvq_t<T_Q4_K,  IDS>(a, act_kind, n, n_pairs, stream); break;
-        case T_Q5_K:  launch_mmvq_t<T_Q5_K,  IDS>(a, act_kind, n, n_pairs, stream); break;
-        case T_Q6_K:  launch_mmvq_t<T_Q6_K,  IDS>(a, act_kind, n, n_pairs, stream); break;
-        case T_MXFP4: launch_mmvq_t<T_MXFP4, IDS>(a, act_kind, n, n_pairs, stream); break;
-        default: fprintf(stderr, "mmvq: unsupported type %d\n", type_a); abort();
+    if (!weight_format_dispatch(type_a, [&](auto t) { launch_mmvq_t<decltype(t)::value, IDS>(a, act_kind, n, n_pairs, stream); })) {
+        fprintf(stderr, "mmvq: unsupported type %d\n", type_a); abort();
     }
 }
 

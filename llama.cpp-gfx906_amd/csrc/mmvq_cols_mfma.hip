@@ -45,13 +45,13 @@ static __device__ __forceinline__ int dot2_i16(int a, int b, int c) {
 }
 
 template <int TYPE> struct colmf_t;
+template <int TYPE> struct colmf_fmt { static constexpr int BLOCK_BYTES = weight_format_of(TYPE).bytes; };
 
 // ---- Q4_K: [d f16][dmin f16][scales 12][qs 128]; sub-block pair P: qs[32P .. 32P+31], low nibbles = sub-block 2P, high = 2P+1.
 //      16-byte loads: load j (0, 1) covers qs[64j .. 64j+63] = pairs 2j, 2j+1; lane group g takes bytes 16g .. 16g+15 of it, i.e. elements
 //      16(g&1) .. +15 of pair 2j + (g>>1): 64 contiguous bytes per row and instruction (8-byte loads, 32 contiguous bytes per row, streamed
 //      at 3 TB/s). An MFMA's four k-groups then carry two different pairs: two MFMAs, each with the other pair's activations zeroed ----
-template <> struct colmf_t<T_Q4_K> {
-    static constexpr int BLOCK_BYTES = 144;
+template <> struct colmf_t<T_Q4_K> : colmf_fmt<T_Q4_K> {
     struct wreg { int4v hdr; int4v q[2]; };
     static __device__ __forceinline__ wreg load(const char * b, int g) {
         wreg w;
@@ -61,8 +61,7 @@ template <> struct colmf_t<T_Q4_K> {
     }
 };
 // ---- Q5_K: [d][dmin][scales 12][qh 32][qs 128]; bit s of qh[e] = 5th bit of element e of sub-block s ----
-template <> struct colmf_t<T_Q5_K> {
-    static constexpr int BLOCK_BYTES = 176;
+template <> struct colmf_t<T_Q5_K> : colmf_fmt<T_Q5_K> {
     struct wreg { int4v hdr; int4v qh; int4v q[2]; };
     static __device__ __forceinline__ wreg load(const char * b, int g) {
         wreg w;
@@ -76,8 +75,7 @@ template <> struct colmf_t<T_Q5_K> {
 //      l+32 = ql[64h+32+l] & 15 | (qh >> 2 & 3) << 4, l+64 = ql[64h+l] >> 4 | (qh >> 4 & 3) << 4, l+96 = ql[64h+32+l] >> 4 | (qh >> 6) << 4;
 //      one int8 scale per 16 elements. The lane of k-group g takes l = 8g .. 8g+7: groups 0, 1 fall into the first scale of each
 //      32-element run, groups 2, 3 into the second ----
-template <> struct colmf_t<T_Q6_K> {
-    static constexpr int BLOCK_BYTES = 210;
+template <> struct colmf_t<T_Q6_K> : colmf_fmt<T_Q6_K> {
     struct wreg { int2v qla[2], qlb[2], qh[2]; int4v sc; uint32_t d; };
     static __device__ __forceinline__ wreg load(const char * b, int g) {
         wreg w;
@@ -316,7 +314,6 @@ bool mul_mat_vec_q_cols_mfma(int type_a, const void * W, size_t w_row_stride, in
                              const act_q8 & act, int64_t n, float * dst, size_t dst_col_stride_bytes, hipStream_t stream) {
     static const int on = (int) env_int("GGML_MI355X_MMVQ_COLS_MFMA", 1);
     if (!on || n < 2 || n > 8 || act.kind != T_Q8_K || k % 256 != 0 || m < 16 || m >= (1ll << 27) || k >= (1ll << 24)) return false;
-    if (type_a != T_Q4_K && type_a != T_Q5_K && type_a != T_Q6_K) return false;
     // Where it pays (rocprofv3 kernel times, 4096 x 14336, profiles/r02_*cols*): this kernel costs ~14 us + 0.4 us per column (its 16-row
     // tiles stream the weights at ~3.5 TB/s: 64 contiguous bytes per row and load instruction), the one-row-pair-per-wave kernel of
     // mmvq.hip ~6 us + 2.5 us per column (VALU). From 5 columns on this one is ahead for Q4_K / Q5_K. Q6_K (16-element scale groups:
@@ -336,11 +333,9 @@ bool mul_mat_vec_q_cols_mfma(int type_a, const void * W, size_t w_row_stride, in
     a.n_tiles = (int)((m + 15)/16);
     static const int dbg = (int) env_int("GGML_MI355X_COLS_DBG", 0);
     a.dbg = dbg;
-    switch (type_a) {
-        case T_Q4_K: return launch_cols_mfma<T_Q4_K>(a, lds, stream);
-        case T_Q5_K: return launch_cols_mfma<T_Q5_K>(a, lds, stream);
-        default:     return launch_cols_mfma<T_Q6_K>(a, lds, stream);
-    }
+    bool taken = false;      // (stays false for a format without a kernel here)
+    dispatch_int<T_Q4_K, T_Q5_K, T_Q6_K>(type_a, [&](auto t) { taken = launch_cols_mfma<decltype(t)::value>(a, lds, stream); });
+    return taken;
 }
 
 } // namespace mi355x

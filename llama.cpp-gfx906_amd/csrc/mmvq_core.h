@@ -42,10 +42,12 @@ static __device__ __forceinline__ void k4_scales(uint32_t s0, uint32_t s1, uint3
 // per-type fragments. LPB = lanes per block; `slot` = lane % LPB; `ib` = block index inside the row
 // ------------------------------------------------------------------------------------------------
 template <int TYPE> struct mmvq_t;
+// what every mmvq_t<TYPE> takes from the list of weight formats (blocks.h)
+template <int TYPE> struct mmvq_fmt { static constexpr int BLOCK_BYTES = weight_format_of(TYPE).bytes, QK = weight_format_of(TYPE).qk, ACT = weight_format_of(TYPE).act; };
 
 // ---- Q4_K ---------------------------------------------------------------------------------------
-template <> struct mmvq_t<T_Q4_K> {
-    static constexpr int LPB = 8, BLOCK_BYTES = 144, QK = 256, ACT = T_Q8_K;
+template <> struct mmvq_t<T_Q4_K> : mmvq_fmt<T_Q4_K> {
+    static constexpr int LPB = 8;
     struct afrag { int4v lo, hi; float d8; int bs_lo, bs_hi; };
     struct wfrag { int4v hdr, qs; };
     static __device__ __forceinline__ afrag load_a(const act_view & a, int64_t ib, int slot) {
@@ -84,8 +86,8 @@ template <> struct mmvq_t<T_Q4_K> {
 };
 
 // ---- Q5_K ---------------------------------------------------------------------------------------
-template <> struct mmvq_t<T_Q5_K> {
-    static constexpr int LPB = 8, BLOCK_BYTES = 176, QK = 256, ACT = T_Q8_K;
+template <> struct mmvq_t<T_Q5_K> : mmvq_fmt<T_Q5_K> {
+    static constexpr int LPB = 8;
     typedef mmvq_t<T_Q4_K>::afrag afrag;
     struct wfrag { int4v hdr, qh, qs; };
     static __device__ __forceinline__ afrag load_a(const act_view & a, int64_t ib, int slot) { return mmvq_t<T_Q4_K>::load_a(a, ib, slot); }
@@ -123,8 +125,8 @@ template <> struct mmvq_t<T_Q5_K> {
 // of the eight-lane split (whose 8-byte loads kept the CU's address unit busy: the workgroups of a Q6_K group ran every phase of the
 // norm+QKV launch ~1.7x slower than their Q4_K neighbours, tools/stamp_timeline.py).
 #ifndef MI_Q6K_LPB8
-template <> struct mmvq_t<T_Q6_K> {
-    static constexpr int LPB = 4, BLOCK_BYTES = 210, QK = 256, ACT = T_Q8_K;
+template <> struct mmvq_t<T_Q6_K> : mmvq_fmt<T_Q6_K> {
+    static constexpr int LPB = 4;
     struct afrag { int4v a[4]; int s[4]; float d8; };   // s[i] = sum of the 16 int8 of a[i] (for the -32 offset)
     struct wfrag { int4v qla, qlb, qh; int2v sc; uint32_t d; };
     static __device__ __forceinline__ afrag load_a(const act_view & a, int64_t ib, int slot) {
@@ -189,8 +191,8 @@ template <> struct mmvq_t<T_Q6_K> {
 // qh[32n + 16(m&1) ..+15], n = j>>2, m = j&3. Its 16 ql bytes are, for m < 2: l = 16m + t -> elements 128n + l (low nibbles, qh bits 0-1)
 // and 128n + 64 + l (high nibbles, qh bits 4-5); for m >= 2: l = 16(m-2) + t -> elements 128n + 32 + l (low, bits 2-3) and 128n + 96 + l
 // (high, bits 6-7) (quants.py:554-572). Each 16-element group is exactly one scale and one Q8_K bsum.
-template <> struct mmvq_t<T_Q6_K> {
-    static constexpr int LPB = 8, BLOCK_BYTES = 210, QK = 256, ACT = T_Q8_K;
+template <> struct mmvq_t<T_Q6_K> : mmvq_fmt<T_Q6_K> {
+    static constexpr int LPB = 8;
     struct afrag { int4v lo, hi; int s_lo, s_hi; float d8; };
     struct wfrag { int4v ql, qh; int2v sc; uint32_t d; };
     static __device__ __forceinline__ afrag load_a(const act_view & a, int64_t ib, int slot) {
@@ -255,8 +257,8 @@ static __device__ __forceinline__ void q3k_scales(uint32_t s0, uint32_t s1, uint
 // covering 32 blocks per step, more than a 4096-long row has.) Rows are 110 nb bytes, 2-byte aligned: unaligned-mode loads as Q6_K's.
 // The 12 scale bytes and d are the block's last 14 bytes: one 16-byte load of bytes 94..109 (the last two of qs in front) stays inside the block.
 // sum q a with q = u - 4, u = low | high << 2 in 0..7: dot(u, a) - 4 bsum16 per group (no dmin term).
-template <> struct mmvq_t<T_Q3_K> {
-    static constexpr int LPB = 4, BLOCK_BYTES = 110, QK = 256, ACT = T_Q8_K;
+template <> struct mmvq_t<T_Q3_K> : mmvq_fmt<T_Q3_K> {
+    static constexpr int LPB = 4;
     struct afrag { int4v a[4]; int s[4]; float d8; };   // s[j] = the Q8_K 16-element sum of a[j]
     struct wfrag { int4v qs, hm, tail; };
     static __device__ __forceinline__ afrag load_a(const act_view & a, int64_t ib, int slot) {
@@ -303,8 +305,8 @@ template <> struct mmvq_t<T_Q3_K> {
 };
 
 // ---- Q8_0 ---------------------------------------------------------------------------------------
-template <> struct mmvq_t<T_Q8_0> {
-    static constexpr int LPB = 2, BLOCK_BYTES = 34, QK = 32, ACT = T_Q8_0;
+template <> struct mmvq_t<T_Q8_0> : mmvq_fmt<T_Q8_0> {
+    static constexpr int LPB = 2;
     struct afrag { int4v a; float d8; };
     struct wfrag { int4v qs; uint32_t d; };
     static __device__ __forceinline__ afrag load_a(const act_view & a, int64_t ib, int slot) {
@@ -326,8 +328,8 @@ template <> struct mmvq_t<T_Q8_0> {
 };
 
 // ---- Q4_0 ---------------------------------------------------------------------------------------
-template <> struct mmvq_t<T_Q4_0> {
-    static constexpr int LPB = 1, BLOCK_BYTES = 18, QK = 32, ACT = T_Q8_0;
+template <> struct mmvq_t<T_Q4_0> : mmvq_fmt<T_Q4_0> {
+    static constexpr int LPB = 1;
     struct afrag { int4v lo, hi; float d8; int bs; };
     struct wfrag { int4v qs; uint32_t d; };
     static __device__ __forceinline__ afrag load_a(const act_view & a, int64_t ib, int) {
@@ -368,8 +370,8 @@ static __device__ __forceinline__ void q5_unpack(const int4v & qs, uint32_t qh, 
 #undef MI_Q5B
 }
 // Q5_0: 22-byte blocks (f16 d | u32 qh | 16 bytes of nibbles), 2-byte aligned; sum (q - 16) a = sum q a - 16 bsum
-template <> struct mmvq_t<T_Q5_0> {
-    static constexpr int LPB = 1, BLOCK_BYTES = 22, QK = 32, ACT = T_Q8_0;
+template <> struct mmvq_t<T_Q5_0> : mmvq_fmt<T_Q5_0> {
+    static constexpr int LPB = 1;
     typedef mmvq_t<T_Q4_0>::afrag afrag;
     struct wfrag { int4v qs; uint32_t d, qh; };
     static __device__ __forceinline__ afrag load_a(const act_view & a, int64_t ib, int slot) { return mmvq_t<T_Q4_0>::load_a(a, ib, slot); }
@@ -390,8 +392,8 @@ template <> struct mmvq_t<T_Q5_0> {
 };
 // Q5_1: 24-byte blocks (f16 d | f16 m | u32 qh | 16 bytes of nibbles), 8-byte aligned; x = d q + m: sumi d d_a + m d_a bsum. (The CPU backend reads
 // s = d_a bsum from a Q8_1 block, rounded to f16; here the product stays in f32.)
-template <> struct mmvq_t<T_Q5_1> {
-    static constexpr int LPB = 1, BLOCK_BYTES = 24, QK = 32, ACT = T_Q8_0;
+template <> struct mmvq_t<T_Q5_1> : mmvq_fmt<T_Q5_1> {
+    static constexpr int LPB = 1;
     typedef mmvq_t<T_Q4_0>::afrag afrag;
     struct wfrag { int4v qs; uint32_t dm, qh; };
     static __device__ __forceinline__ afrag load_a(const act_view & a, int64_t ib, int slot) { return mmvq_t<T_Q4_0>::load_a(a, ib, slot); }
@@ -424,8 +426,8 @@ static __device__ __forceinline__ int mxfp4_lut4(uint32_t idx) {
     return (int)((p & ~m) | (n & m));
 }
 
-template <> struct mmvq_t<T_MXFP4> {
-    static constexpr int LPB = 1, BLOCK_BYTES = 17, QK = 32, ACT = T_Q8_0;
+template <> struct mmvq_t<T_MXFP4> : mmvq_fmt<T_MXFP4> {
+    static constexpr int LPB = 1;
     struct afrag { int4v lo, hi; float d8; };
     struct wfrag { int4v qs; uint32_t e; };
     static __device__ __forceinline__ afrag load_a(const act_view & a, int64_t ib, int) {

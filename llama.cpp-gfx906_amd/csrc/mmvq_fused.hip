@@ -222,13 +222,20 @@ static fused_launch fused_prepare(const mmvq_group * groups, int n_groups, int64
     return L;
 }
 
-// the formats fused_launch_kernel has register-ring kernels for
-static bool fused_ring_has(int type) {
-    switch (type) {
-        case T_Q4_K: case T_Q5_K: case T_Q6_K: case T_Q8_0: case T_Q4_0: case T_MXFP4: return true;
-        default: return false;
-    }
+// THE table of weight-type pairs (ta <= tb) that have a register-ring kernel family (mmvq_fused_<format>.hip), as st_pairs[] is for the streamed kernels. Mixed rows
+// serve launches without a GLU group only; pro_q8: the row also serves a launch that is handed a ready-made image (two activation formats cannot share one)
+struct fused_pair { int ta, tb; void (*launch)(const fused_launch &, hipStream_t); bool pro_q8; };
+static const fused_pair fused_pairs[] = {
+    { T_Q4_K, T_Q4_K, launch_fused_q4_K, true }, { T_Q5_K, T_Q5_K, launch_fused_q5_K, true }, { T_Q6_K, T_Q6_K, launch_fused_q6_K, true },
+    { T_Q8_0, T_Q8_0, launch_fused_q8_0, true }, { T_Q4_0, T_Q4_0, launch_fused_q4_0, true }, { T_MXFP4, T_MXFP4, launch_fused_mxfp4, true },
+    { T_Q4_K, T_Q5_K, launch_fused_q4_K_q5_K, true }, { T_Q4_K, T_Q6_K, launch_fused_q4_K_q6_K, true }, { T_Q5_K, T_Q6_K, launch_fused_q5_K_q6_K, true },
+    { T_Q8_0, T_Q4_K, launch_fused_q8_0_q4_K, false },
+};
+static const fused_pair * fused_pair_of(int ta, int tb) {
+    for (const fused_pair & r : fused_pairs) if (r.ta == ta && r.tb == tb) return &r;
+    return nullptr;
 }
+static bool fused_ring_has(int type) { return fused_pair_of(type, type) != nullptr; }
 bool mul_mat_vec_q_fused_takes(const mmvq_group * groups, int n_groups, int64_t k, const mmvq_input & in, const mmvq_rope * rope) {
     bool ring = true;
     for (int i = 0; i < n_groups; i++) ring = ring && fused_ring_has(groups[i].type);
@@ -238,24 +245,9 @@ bool mul_mat_vec_q_fused_takes(const mmvq_group * groups, int n_groups, int64_t 
 }
 
 static void fused_launch_kernel(const fused_launch & L, hipStream_t stream) {
-    const int ta = L.ta, tb = L.tb;
-    if (ta == tb) {
-        switch (ta) {
-            case T_Q4_K:  launch_fused_q4_K(L, stream); return;
-            case T_Q5_K:  launch_fused_q5_K(L, stream); return;
-            case T_Q6_K:  launch_fused_q6_K(L, stream); return;
-            case T_Q8_0:  launch_fused_q8_0(L, stream); return;
-            case T_Q4_0:  launch_fused_q4_0(L, stream); return;
-            case T_MXFP4: launch_fused_mxfp4(L, stream); return;
-            default: break;
-        }
-    } else if (!L.glu) {
-        if (ta == T_Q4_K && tb == T_Q5_K) { launch_fused_q4_K_q5_K(L, stream); return; }
-        if (ta == T_Q4_K && tb == T_Q6_K) { launch_fused_q4_K_q6_K(L, stream); return; }
-        if (ta == T_Q5_K && tb == T_Q6_K) { launch_fused_q5_K_q6_K(L, stream); return; }
-        if (ta == T_Q8_0 && tb == T_Q4_K && L.mode != PRO_Q8) { launch_fused_q8_0_q4_K(L, stream); return; }
-    }
-    fprintf(stderr, "mul_mat_vec_q_fused: type pair (%d, %d) has no kernel (check mul_mat_vec_q_fused_can_group)\n", ta, tb);
+    const fused_pair * pair = fused_pair_of(L.ta, L.tb);
+    if (pair && (L.ta == L.tb || !L.glu) && (pair->pro_q8 || L.mode != PRO_Q8)) { pair->launch(L, stream); return; }
+    fprintf(stderr, "mul_mat_vec_q_fused: type pair (%d, %d) has no kernel for this launch (fused_pairs[])\n", L.ta, L.tb);
     abort();
 }
 
@@ -275,17 +267,22 @@ void mul_mat_vec_q_fused(const mmvq_group * groups, int n_groups, int64_t k, con
     fused_launch_kernel(L, stream);
 }
 
-// which weight types may share one grouped launch (the mixtures llama_tensor_get_type produces, src/llama-quant.cpp:178-434)
+// which weight types may share one grouped launch (the mixtures llama_tensor_get_type produces, src/llama-quant.cpp:178-434): the same type, or two of one
+// activation format that either table has a kernel for (the Q3_K mixes: streamed kernel only)
 bool mul_mat_vec_q_fused_can_group(int type_a, int type_b) {
     if (type_a == type_b) return true;
-    const int lo = type_a < type_b ? type_a : type_b, hi = type_a < type_b ? type_b : type_a;
-    if (lo == T_Q3_K) return hi == T_Q4_K || hi == T_Q5_K;      // (Q3_K_M / _L: wq, wk beside wv — streamed kernel only; Q3_K + Q6_K has no kernel)
-    return (lo == T_Q4_K && (hi == T_Q5_K || hi == T_Q6_K)) || (lo == T_Q5_K && hi == T_Q6_K);
+    const int lo = std::min(type_a, type_b), hi = std::max(type_a, type_b);
+    return act_kind_for(lo) == act_kind_for(hi) && (fused_pair_of(lo, hi) || mul_mat_vec_q_stream_has_pair(lo, hi));
 }
-// ... and which pairs of DIFFERENT activation formats may, when every workgroup quantizes the activation itself (PRO_QUANT / PRO_NORM)
-bool mul_mat_vec_q_fused_can_group_mixed(int type_a, int type_b) {
-    const int lo = type_a < type_b ? type_a : type_b, hi = type_a < type_b ? type_b : type_a;
-    return lo == T_Q8_0 && hi == T_Q4_K;
+// ... and which pairs of DIFFERENT activation formats may, when every workgroup quantizes the activation itself (PRO_QUANT / PRO_NORM). Stated, not derived:
+// st_pairs[] also holds Q8_0 + Q6_K, a pair the matchers are not offered
+bool mul_mat_vec_q_fused_can_group_mixed(int type_a, int type_b) { return std::min(type_a, type_b) == T_Q8_0 && std::max(type_a, type_b) == T_Q4_K; }
+
+// diagnostic export (no device needed; tests/test_weight_format_table.py): what the host code answers about weight type a — out[0] supported, [1] activation
+// kind or -1, [2] elements and [3] bytes per block (0: not a weight format), [4] has a register-ring kernel — and about the pair (a, b): [5] can_group, [6] can_group_mixed
+extern "C" void mi355x_weight_format_info(int type_a, int type_b, int * out) {
+    out[0] = mul_mat_vec_q_supported(type_a); out[1] = act_kind_for(type_a); out[2] = weight_format_of(type_a).qk; out[3] = weight_format_of(type_a).bytes;
+    out[4] = fused_ring_has(type_a); out[5] = mul_mat_vec_q_fused_can_group(type_a, type_b); out[6] = mul_mat_vec_q_fused_can_group_mixed(type_a, type_b);
 }
 
 } // namespace mi355x

@@ -564,6 +564,13 @@ template <> struct st_unit<ST_MXFP4_B10> {
     }
 };
 
+// UB is written per unit above because a unit is not always one block: it is 256 weights — one K-quant block, eight 32-element blocks — or ten 32-element
+// blocks in the two pseudo types. Against the list of weight formats (blocks.h):
+template <int TYPE, int UTYPE = TYPE> constexpr bool st_unit_bytes_ok(int weights) { return st_unit<UTYPE>::UB == weights/weight_format_of(TYPE).qk*weight_format_of(TYPE).bytes; }
+static_assert(st_unit_bytes_ok<T_Q3_K>(256) && st_unit_bytes_ok<T_Q4_K>(256) && st_unit_bytes_ok<T_Q5_K>(256) && st_unit_bytes_ok<T_Q6_K>(256), "a K-quant unit is one block");
+static_assert(st_unit_bytes_ok<T_Q4_0>(256) && st_unit_bytes_ok<T_Q5_0>(256) && st_unit_bytes_ok<T_Q5_1>(256) && st_unit_bytes_ok<T_Q8_0>(256), "a 32-element format's unit is eight blocks");
+static_assert(st_unit_bytes_ok<T_Q8_0, ST_Q8_0_B10>(320) && st_unit_bytes_ok<T_MXFP4, ST_MXFP4_B10>(320), "a ten-block unit");
+
 constexpr int ST_NSTAMP = 16;      // stamps per wave (diagnostic builds)
 #ifdef MI_STAMPS
 #define ST_STAMP(i_) do { if (stamps && lane == 0) __hip_atomic_store(&stamps[((size_t) blockIdx.x*(ST_NC + 1) + wave)*ST_NSTAMP + (i_)], (unsigned long long) __builtin_amdgcn_s_memrealtime(), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); } while (0)
@@ -1216,5 +1223,6 @@ struct st_plan {
 };
 st_plan mul_mat_vec_q_stream_plan(const mmvq_group * groups, int n_groups, int64_t k, const mmvq_input & in, const mmvq_rope * rope);
 void mul_mat_vec_q_stream(const st_plan & plan, hipStream_t stream, mmvq_launch_rec * rec = nullptr);      // plan.ok only
+bool mul_mat_vec_q_stream_has_pair(int type_a, int type_b);      // does st_pairs[] hold a kernel for two groups of these weight types (either order)
 
 } // namespace mi355x

@@ -37,6 +37,7 @@ static const st_pair * st_pair_of(int ta, int tb) {
     for (const st_pair & r : st_pairs) if (r.ta == ta && r.tb == tb) return &r;
     return nullptr;
 }
+bool mul_mat_vec_q_stream_has_pair(int type_a, int type_b) { return st_pair_of(std::min(type_a, type_b), std::max(type_a, type_b)) != nullptr; }
 static int st_unit_bytes(int utype) { const st_pair * r = st_pair_of(utype, utype); return r ? r->ub_a : 0; }      // (every unit type has a same-type row)
 // the unit a weight type is streamed in at row length k: 256 weights, or ten 32-blocks where k is not a multiple of 256 (gpt-oss: 2880); 0: none
 static int st_utype(int type, int64_t k) {
@@ -99,7 +100,7 @@ st_plan mul_mat_vec_q_stream_plan(const mmvq_group * groups, int n_groups, int64
     for (int i = 0; i < n_groups; i++) {
         const mmvq_group & g = groups[i];
         ut[i] = st_utype(g.type, k); ub[i] = st_unit_bytes(ut[i]);
-        if (!ub[i] || (act_kind_for(g.type) == T_Q8_0 && in.mode == PRO_Q8)) return P;      // (Q8_0, Q4_0, Q5_0, Q5_1 units read the Q8_0 image only the launch's own prologue builds)
+        if (!ub[i] || (act_kind_for(g.type) == T_Q8_0 && in.mode == PRO_Q8)) return P;      // (units of a Q8_0-activation format read the Q8_0 image only the launch's own prologue builds)
         if (ut[i] != ta && ut[i] != tb) { if (ta < 0) ta = ut[i]; else if (tb < 0) tb = ut[i]; else return P; }
         if (b10 && tb >= 0) return P;                              // (one kernel per ten-block format: no mixed launches)
         if ((g.b_gate != nullptr) != (g.b_up != nullptr) || (g.b_gate && (g.epi != EPI_GLU || !g.eid)) || (g.res_eid && (g.epi != EPI_ADD || !g.eid))) return P;

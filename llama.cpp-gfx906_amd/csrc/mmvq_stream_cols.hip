@@ -151,6 +151,11 @@ static void stc_launch(const st_args & a, const st_cols & c, int blocks, size_t 
     MI_LDS_LIMIT_OR_DIE(MI_LDS_BUDGET, k_mmvq_stream_cols<TYPE, N, true>);
     hipLaunchKernelGGL((k_mmvq_stream_cols<TYPE, N, true>), dim3((unsigned) blocks), dim3(ST_THREADS), lds, stream, a, c);
 }
+// the instantiation for N = 2, 4 or 8 column slots
+template <int TYPE>
+static void stc_launch_n(int N, const st_args & a, const st_cols & c, int blocks, size_t lds, hipStream_t stream) {
+    dispatch_int<2, 4, 8>(N, [&](auto nc) { stc_launch<TYPE, decltype(nc)::value>(a, c, blocks, lds, stream); });
+}
 
 // false = not taken (format, shape, LDS): the caller runs another kernel
 bool mul_mat_vec_q_stream_cols(int type_a, const void * W, size_t w_row_stride, int64_t m, int64_t k,
@@ -161,8 +166,11 @@ bool mul_mat_vec_q_stream_cols(int type_a, const void * W, size_t w_row_stride, 
     // Q4_K's per column (6-bit unpack, 16-element scale groups) and the kernel is instruction-bound from 3 columns on: 23.7 / 24.1 / 39.9 us at
     // n = 3 / 4 / 5 (4096 x 14336) against 17.7 / 19.6 / 20.7 for the kernels it would replace
     if (type_a == T_Q6_K && on < 2) return false;
-    const int ub = type_a == T_Q4_K ? 144 : type_a == T_Q5_K ? 176 : type_a == T_Q6_K ? 210 : 0;
-    if (!ub || k % 2048 != 0 || k > 16384 || m < 1 || m >= (1ll << 23)) return false;       // (a row's blocks in groups of 8 or 16 lanes)
+    // the formats with a kernel here (a unit of theirs is one block)
+    void (*launch)(int, const st_args &, const st_cols &, int, size_t, hipStream_t) = nullptr;
+    dispatch_int<T_Q4_K, T_Q5_K, T_Q6_K>(type_a, [&](auto t) { launch = stc_launch_n<decltype(t)::value>; });
+    const int ub = weight_format_of(type_a).bytes;
+    if (!launch || k % 2048 != 0 || k > 16384 || m < 1 || m >= (1ll << 23)) return false;       // (a row's blocks in groups of 8 or 16 lanes)
     const int nb = (int)(k/256);
     if (w_row_stride != (size_t) nb*ub || ((uintptr_t) W % 16) || ((uintptr_t) act.qs % 16) || ((uintptr_t) act.bsums % 16) || ((uintptr_t) dst % 4) || dst_col_stride_bytes % 4) return false;
     st_args a = st_args{};
@@ -195,9 +203,7 @@ bool mul_mat_vec_q_stream_cols(int type_a, const void * W, size_t w_row_stride, 
     if (S > ST_MAX_RING) S = ST_MAX_RING;
     a.S = S;
     const size_t lds = fixed + (size_t) S*slot;
-#define MI_STC(T_) do { if (N == 2) stc_launch<T_, 2>(a, c, blocks, lds, stream); else if (N == 4) stc_launch<T_, 4>(a, c, blocks, lds, stream); else stc_launch<T_, 8>(a, c, blocks, lds, stream); } while (0)
-    if (type_a == T_Q4_K) MI_STC(T_Q4_K); else if (type_a == T_Q5_K) MI_STC(T_Q5_K); else MI_STC(T_Q6_K);
-#undef MI_STC
+    launch(N, a, c, blocks, lds, stream);
     return true;
 }
 

@@ -16,13 +16,7 @@ namespace mi355x {
 
 static inline size_t pad256(size_t x) { return (x + 255) & ~(size_t) 255; }
 
-int act_kind_for(int type_a) {
-    switch (type_a) {
-        case T_Q4_0: case T_Q5_0: case T_Q5_1: case T_Q8_0: case T_MXFP4: return T_Q8_0;
-        case T_Q3_K: case T_Q4_K: case T_Q5_K: case T_Q6_K:  return T_Q8_K;
-        default: return -1;
-    }
-}
+int act_kind_for(int type_a) { return weight_format_of(type_a).act; }
 
 size_t act_q8_bytes(int kind, int64_t k, int64_t n) {
     const int64_t nd  = kind == T_Q8_0 ? k/32 : k/256;

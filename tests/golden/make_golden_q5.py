@@ -8,7 +8,7 @@ Run ONLY in the build container (the reference tree does not travel to the GPU b
 
 Writes dequant_q5_0.npz, dequant_q5_1.npz (blocks, expected) and quant_q5_0.npz, quant_q5_1.npz (x, expected).
 The committed .npz files are DATA (inputs + expected outputs); nothing here copies reference source text.
-tests/test_q5_formats.py checks its own numpy restatement of both formats against them bit for bit.
+tests/test_q5_formats.py checks the numpy restatement of both formats (tests/weight_formats.py) against them bit for bit.
 
 Block layouts (little-endian):  Q5_0 = f16 d | u32 qh | 16 B qs;   Q5_1 = f16 d | f16 m | u32 qh | 16 B qs.
 Edge blocks of the dequant fixtures: all zero; qh all ones; qh alternating (0xAAAAAAAA, 0x55555555); an f16-subnormal d;

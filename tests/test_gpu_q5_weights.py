@@ -1,300 +1,74 @@
 """GPU parity for Q5_0 / Q5_1 weights — the 32-element formats llama_tensor_get_type writes in place of Q4_K / Q5_K when a row is
-not a multiple of 256 long (src/llama-quant.cpp:436-470) — in MUL_MAT and MUL_MAT_ID, through the backend's C-ABI.
+not a multiple of 256 long (src/llama-quant.cpp:436-470) — in MUL_MAT and MUL_MAT_ID: the parameter lines. The case bodies, the reference
+and the gates are tests/gpu_weight_format_cases.py's.
 
-The oracle knows six formats; this file carries its own reference: tests/test_q5_formats.py's numpy quantizer / dequantizer (pinned bit
-for bit against the golden vectors there), expected values = dequant(W) @ X in float64, gate = the reference's MUL_MAT gate
-NMSE <= 5e-4 (tests/test-backend-ops.cpp:3106-3108, as throughout tests/test_gpu_mul_mat.py). Weights are quant(U(-1, 1)), fixed seeds.
-Every case first asserts supports_op.
-
-Shapes (the smallest at which each path can go wrong):
-  k = 32 (one block), 288 (nine blocks: k % 256 != 0, odd block count, a wave's tail), 1024 (four streamed units), 1280 (five: odd);
-  m = 1, 33, 130 (fewer rows than a workgroup's waves x 2, a row tail, more than one 128-row prefill tile);
-  n = 1 (streamed / simple decode kernel; fusion off: the simple kernel at every k), 2, 5, 8 (the column forms), 9, 33, 130 (prefill tiles
-  with row and column tails).
+  k = 32 (one block), 288 (nine blocks: k % 256 != 0, odd block count, a wave's tail), 1024 (four streamed units), 1280 (five: odd)
 """
-import numpy as np
 import pytest
 
-from gpu_util import backend, gg, run_mul_mat, run_mul_mat_bcast
-from test_q5_formats import DEQUANT, NAMES, QUANT
+import gpu_weight_format_cases as cases
 
 pytestmark = pytest.mark.gpu
-L = gg.base()
-
-GATE = 5e-4
-QT = dict(NAMES)      # enum ggml_type 6 and 7 (spelled out, so that without the two formats a case fails at its supports_op assertion, not at import)
-
-
-def nmse(expected, got):
-    e = np.asarray(expected, np.float64); g = np.asarray(got, np.float64)
-    return float(((e - g)**2).sum() / ((e**2).sum() + 1e-300))
-
-
-def weights(rng, name, shape, k):
-    """quant(U(-1, 1)) [*shape, row_bytes] u8 and its dequantization [*shape, k] f64"""
-    w = QUANT[NAMES[name]](rng.uniform(-1, 1, size=(*shape, k)).astype(np.float32))
-    return w, DEQUANT[NAMES[name]](w).astype(np.float64)
-
-
-def probe(name, k, m, n):
-    """what llama.cpp asks at load time (and what fails without the two formats)"""
-    be = backend()
-    with gg.Context() as ctx:
-        out = L.ggml_mul_mat(ctx.ctx, ctx.new_tensor(QT[name], [k, m]), ctx.new_tensor(gg.F32, [k, n]))
-        assert be.supports_op(out), f"{name}: MUL_MAT refused"
+NAMES = ["q5_0", "q5_1"]
 
 
 @pytest.mark.parametrize("m", [1, 33, 130])
 @pytest.mark.parametrize("k", [32, 288, 1024, 1280])
-@pytest.mark.parametrize("name", list(QT))
+@pytest.mark.parametrize("name", NAMES)
 def test_mul_mat(name, k, m):
-    probe(name, k, m, 512)
-    rng = np.random.default_rng(1000*k + m)
-    w, wd = weights(rng, name, (m,), k)
-    xs = rng.uniform(-1, 1, size=(130, k)).astype(np.float32)
-    be = backend()
-    for n in (1, 2, 5, 8, 9, 33, 130):
-        x = xs[:n]
-        exp = x.astype(np.float64) @ wd.T
-        for fusion in ((1, 0) if n == 1 else (1,)):
-            be.set_option("fusion", fusion)
-            try:
-                got = run_mul_mat(QT[name], w, x, m, k)
-            finally:
-                be.set_option("fusion", 1)
-            e = nmse(exp, got)
-            print(f"{name} k={k} m={m} n={n} fusion={fusion}: NMSE {e:.3g}")
-            assert np.isfinite(got).all() and e <= GATE, (name, k, m, n, fusion, e)
+    cases.check_mul_mat(name, k, m)
 
 
 @pytest.mark.parametrize("k,m", [(4096, 300), (14336, 4096)])
-@pytest.mark.parametrize("name", list(QT))
+@pytest.mark.parametrize("name", NAMES)
 def test_mul_mat_one_column_at_model_row_lengths(name, k, m):
-    """the streamed kernel where its other branches run: k / 256 = 16 units per row (the 16-lane row reduction), and the ffn_down shape whose workgroups
-    stream more slots (14) than the LDS ring holds, so that slots are reused. (The 4096 rows are 256 quantized rows repeated: the numpy quantizer is the slow part.)"""
-    probe(name, k, m, 512)
-    rng = np.random.default_rng(k + m)
-    base, based = weights(rng, name, (min(m, 256),), k)
-    reps = -(-m // base.shape[0])
-    w = np.tile(base, (reps, 1))[:m]; wd = np.tile(based, (reps, 1))[:m]
-    x = rng.uniform(-1, 1, size=(1, k)).astype(np.float32)
-    got = run_mul_mat(QT[name], w, x, m, k)
-    e = nmse(x.astype(np.float64) @ wd.T, got)
-    print(f"{name} k={k} m={m} n=1: NMSE {e:.3g}")
-    assert np.isfinite(got).all() and e <= GATE
+    cases.check_mul_mat_one_column_at_model_row_lengths(name, k, m)
 
 
-@pytest.mark.parametrize("name", list(QT))
+@pytest.mark.parametrize("name", NAMES)
 def test_one_column_runs_on_the_streamed_kernel(name):
-    """k % 256 == 0: the decode launch is the streamed kernel's instantiation for the format (DESIGN.md §4 has the measurement behind that route);
-    k % 256 != 0: it declines and the generic kernel runs (no grouped-launch record)."""
-    rng = np.random.default_rng(4)
-    be = backend()
-    m = 130
-    be.set_option("graphs", 0); be.set_option("fusion", 1); be.set_option("profile", 1)
-    try:
-        for k in (1024, 288):
-            w, wd = weights(rng, name, (m,), k)
-            x = rng.uniform(-1, 1, size=(1, k)).astype(np.float32)
-            got = run_mul_mat(QT[name], w, x, m, k)
-            assert nmse(x.astype(np.float64) @ wd.T, got) <= GATE
-        prof = [e for e in be.profile(64) if e["type"] == QT[name]]
-    finally:
-        be.set_option("profile", 0); be.set_option("graphs", 1)
-    t = QT[name]
-    grouped = {e["k"]: e["kernel"] for e in prof if e["m"] < 0}
-    assert grouped.get(1024, "").startswith(f"k_mmvq_stream<{t}, {t},"), prof
-    assert 288 not in grouped and any(e["k"] == 288 and e["m"] == m for e in prof), prof
+    cases.check_one_column_runs_on_the_streamed_kernel(name, (1024, 288))
 
 
 @pytest.mark.parametrize("n", [1, 3, 40])
-@pytest.mark.parametrize("name", list(QT))
+@pytest.mark.parametrize("name", NAMES)
 def test_mul_mat_f16_src1(name, n):
-    """tests/test-backend-ops.cpp:5715-5716: F16 activations"""
-    rng = np.random.default_rng(77 + n)
-    m, k = 33, 288
-    be = backend()
-    w, wd = weights(rng, name, (m,), k)
-    x16 = rng.uniform(-1, 1, size=(n, k)).astype(np.float16)
-    with gg.Context() as ctx:
-        a = ctx.new_tensor(QT[name], [k, m]); b = ctx.new_tensor(gg.F16, [k, n])
-        out = L.ggml_mul_mat(ctx.ctx, a, b)
-        assert be.supports_op(out)
-        assert ctx.alloc(be)
-        gg.tensor_set(a, w); gg.tensor_set(b, x16)
-        be.compute(gg.graph_of(ctx, out))
-        got = gg.tensor_get(out)[0, 0].copy()
-    e = nmse(x16.astype(np.float64) @ wd.T, got)
-    print(f"{name} f16 src1 n={n}: NMSE {e:.3g}")
-    assert np.isfinite(got).all() and e <= GATE
+    cases.check_mul_mat_f16_src1(name, 288, n)
 
 
 @pytest.mark.parametrize("n", [1, 3])
-@pytest.mark.parametrize("name", list(QT))
+@pytest.mark.parametrize("name", NAMES)
 def test_mul_mat_broadcast(name, n):
-    """ne02 = 2, ne12 = 4: dst[.., i2] = a[.., i2 / 2] . b[.., i2] — the batched mat-vec launch"""
-    rng = np.random.default_rng(5 + n)
-    m, k, bs, nr = 33, 288, (2, 1), (2, 1)
-    w, wd = weights(rng, name, (1, 2, m), k)
-    x = rng.uniform(-1, 1, size=(1, 4, n, k)).astype(np.float32)
-    with gg.Context() as ctx:
-        assert backend().supports_op(L.ggml_mul_mat(ctx.ctx, ctx.new_tensor(QT[name], [k, m, 2, 1]), ctx.new_tensor(gg.F32, [k, n, 4, 1])))
-    got = run_mul_mat_bcast(QT[name], w, x, m, k, bs, nr)
-    assert got.shape == (1, 4, n, m)
-    for i2 in range(4):
-        e = nmse(x[0, i2].astype(np.float64) @ wd[0, i2 // 2].T, got[0, i2])
-        print(f"{name} broadcast n={n} batch {i2}: NMSE {e:.3g}")
-        assert e <= GATE
+    cases.check_mul_mat_broadcast(name, 288, n)
 
 
 @pytest.mark.parametrize("k,n", [(1024, 1), (288, 4), (288, 40)])
-@pytest.mark.parametrize("name", list(QT))
+@pytest.mark.parametrize("name", NAMES)
 def test_mul_mat_twice_is_bitwise_equal(name, k, n):
-    """the same graph computed twice with graph capture on: the second compute replays the captured launches"""
-    rng = np.random.default_rng(k + n)
-    m = 130
-    be = backend()
-    w, wd = weights(rng, name, (m,), k)
-    x = rng.uniform(-1, 1, size=(n, k)).astype(np.float32)
-    be.set_option("graphs", 1); be.set_option("fusion", 1)
-    with gg.Context() as ctx:
-        a = ctx.new_tensor(QT[name], [k, m]); b = ctx.new_tensor(gg.F32, [k, n])
-        out = L.ggml_mul_mat(ctx.ctx, a, b)
-        assert be.supports_op(out)
-        assert ctx.alloc(be)
-        gg.tensor_set(a, w); gg.tensor_set(b, x)
-        graph = gg.graph_of(ctx, out)
-        be.compute(graph); first = gg.tensor_get(out)[0, 0].copy()
-        L.ggml_backend_tensor_memset(out, 0xFF, 0, L.ggml_nbytes(out))
-        be.compute(graph); second = gg.tensor_get(out)[0, 0].copy()
-    assert nmse(x.astype(np.float64) @ wd.T, first) <= GATE
-    assert np.array_equal(first.view(np.uint32), second.view(np.uint32))
+    cases.check_mul_mat_twice_is_bitwise_equal(name, k, n)
 
 
 @pytest.mark.parametrize("n_tokens", [1, 3, 35])
 @pytest.mark.parametrize("k", [288, 1024])
-@pytest.mark.parametrize("name", list(QT))
+@pytest.mark.parametrize("name", NAMES)
 def test_mul_mat_id(name, k, n_tokens):
-    """4 experts, 2 used; ids = a strided view of a shuffled [n_expert, n_tokens] tensor (tests/test-backend-ops.cpp:3231-3236).
-    One token: decode pairs (the grouped launch over the expert stack where the streamed kernel takes it); 3 tokens: the mat-vec _id form;
-    35 tokens: 70 pairs sorted by expert through the prefill tiles."""
-    rng = np.random.default_rng(31*k + n_tokens)
-    n_expert, n_used, m = 4, 2, 33
-    be = backend()
-    w, wd = weights(rng, name, (n_expert, m), k)
-    ids_full = np.stack([rng.permutation(n_expert) for _ in range(n_tokens)]).astype(np.int32)
-    b_ = rng.uniform(-1, 1, size=(1, n_tokens, n_used, k)).astype(np.float32)
-    exp = np.einsum("tumk,tuk->tum", wd[ids_full[:, :n_used]], b_[0].astype(np.float64))
-    for fusion in (1, 0):
-        be.set_option("fusion", fusion)
-        try:
-            with gg.Context() as ctx:
-                as_ = ctx.new_tensor(QT[name], (k, m, n_expert)); ids = ctx.new_tensor(gg.I32, (n_expert, n_tokens)); b = ctx.new_tensor(gg.F32, (k, n_used, n_tokens))
-                idv = L.ggml_view_2d(ctx.ctx, ids, n_used, n_tokens, n_expert*4, 0)
-                out = L.ggml_mul_mat_id(ctx.ctx, as_, b, idv)
-                assert be.supports_op(out), f"{name}: MUL_MAT_ID refused"
-                assert ctx.alloc(be)
-                gg.tensor_set(as_, w); gg.tensor_set(ids, ids_full.reshape(1, 1, n_tokens, n_expert)); gg.tensor_set(b, b_)
-                be.compute(gg.graph_of(ctx, out))
-                got = gg.tensor_get(out)[0].copy()
-        finally:
-            be.set_option("fusion", 1)
-        e = nmse(exp, got)
-        print(f"{name} MUL_MAT_ID k={k} tokens={n_tokens} fusion={fusion}: NMSE {e:.3g}")
-        assert got.shape == exp.shape and np.isfinite(got).all() and e <= GATE
-
-
-def _ffn_f64(x, wn, wg, wu, wd, eps):
-    x = x.astype(np.float64)
-    h = x / np.sqrt((x*x).mean(axis=-1, keepdims=True) + eps) * wn.astype(np.float64)
-    g = h @ wg.T; u = h @ wu.T
-    return (g / (1.0 + np.exp(-g)) * u) @ wd.T + x
+    cases.check_mul_mat_id(name, k, n_tokens)
 
 
 @pytest.mark.parametrize("T", [1, 4, 40])
 @pytest.mark.parametrize("n_embd,n_ff", [(288, 768), (1024, 2048)])
 def test_ffn_subgraph_fused_and_unfused(n_embd, n_ff, T):
-    """RMS_NORM -> MUL(weight) -> gate / up MUL_MAT (Q5_0) -> GLU(swiglu) -> down MUL_MAT (Q5_1) -> ADD(residual), with the fusion pass on and
-    off: a matcher that routed one of the two formats into a launcher without it would abort or disagree. Both runs within the gate against
-    float64, and within 5e-4 (NMSE) of each other."""
-    rng = np.random.default_rng(n_embd + T)
-    be = backend()
-    x = rng.standard_normal((T, n_embd)).astype(np.float32)
-    wn = rng.uniform(0.5, 1.5, size=(n_embd,)).astype(np.float32)
-    wg, wgd = weights(rng, "q5_0", (n_ff,), n_embd); wu, wud = weights(rng, "q5_0", (n_ff,), n_embd)
-    wd, wdd = weights(rng, "q5_1", (n_embd,), n_ff)
-    exp = _ffn_f64(x, wn, wgd, wud, wdd, 1e-5)
-    res = {}
-    for fusion in (1, 0):
-        be.set_option("fusion", fusion)
-        try:
-            with gg.Context() as ctx:
-                xt = ctx.new_tensor(gg.F32, (n_embd, T)); wt = ctx.new_tensor(gg.F32, (n_embd,))
-                g_ = ctx.new_tensor(QT["q5_0"], (n_embd, n_ff)); u_ = ctx.new_tensor(QT["q5_0"], (n_embd, n_ff)); d_ = ctx.new_tensor(QT["q5_1"], (n_ff, n_embd))
-                nm = L.ggml_mul(ctx.ctx, L.ggml_rms_norm(ctx.ctx, xt, 1e-5), wt)
-                gate = L.ggml_mul_mat(ctx.ctx, g_, nm); up = L.ggml_mul_mat(ctx.ctx, u_, nm)
-                assert be.supports_op(gate) and be.supports_op(up)
-                act = L.ggml_swiglu_split(ctx.ctx, gate, up)
-                down = L.ggml_mul_mat(ctx.ctx, d_, act)
-                assert be.supports_op(down)
-                out = L.ggml_add(ctx.ctx, down, xt)
-                assert ctx.alloc(be)
-                gg.tensor_set(xt, x.reshape(1, 1, T, n_embd)); gg.tensor_set(wt, wn.reshape(1, 1, 1, n_embd))
-                gg.tensor_set(g_, wg); gg.tensor_set(u_, wu); gg.tensor_set(d_, wd)
-                be.compute(gg.graph_of(ctx, out))
-                res[fusion] = gg.tensor_get(out)[0, 0].copy()
-        finally:
-            be.set_option("fusion", 1)
-    e1, e0, e10 = nmse(exp, res[1]), nmse(exp, res[0]), nmse(res[0], res[1])
-    print(f"FFN {n_embd}/{n_ff} T={T}: NMSE fused {e1:.3g}, unfused {e0:.3g}, fused vs unfused {e10:.3g}")
-    assert np.isfinite(res[1]).all() and np.isfinite(res[0]).all()
-    assert e1 <= GATE and e0 <= GATE
-    assert e10 <= 5e-4
+    """gate / up Q5_0, down Q5_1, the one-mat-mul gate"""
+    cases.check_ffn_subgraph_fused_and_unfused("q5_0", "q5_1", n_embd, n_ff, cases.GATE, T)
 
 
 @pytest.mark.parametrize("k", [288, 1024])
 @pytest.mark.parametrize("types", [("q5_0", "q5_0", "q5_0"), ("q5_1", "q5_1", "q5_1"), ("q5_0", "q5_1", "q5_0")])
 def test_mat_vecs_on_one_normed_activation(types, k):
-    """RMS_NORM -> MUL(weight) -> three mat-vecs that read the product (wq / wk / wv of a decode step): with the fusion pass on, same-format
-    neighbours share one grouped launch (streamed at k % 256 == 0) and a Q5_0 / Q5_1 neighbour pair, which has no common kernel, splits it."""
-    rng = np.random.default_rng(k + len(set(types)))
-    be = backend()
-    ms = (130, 66, 34)
-    x = rng.standard_normal((1, k)).astype(np.float32); wn = rng.uniform(0.5, 1.5, size=(k,)).astype(np.float32)
-    ws = [weights(rng, t, (m,), k) for t, m in zip(types, ms)]
-    h = x.astype(np.float64) / np.sqrt((x.astype(np.float64)**2).mean() + 1e-5) * wn
-    res = {}
-    for fusion in (1, 0):
-        be.set_option("fusion", fusion)
-        try:
-            with gg.Context() as ctx:
-                xt = ctx.new_tensor(gg.F32, (k, 1)); wt = ctx.new_tensor(gg.F32, (k,))
-                wts = [ctx.new_tensor(QT[t], (k, m)) for t, m in zip(types, ms)]
-                nm = L.ggml_mul(ctx.ctx, L.ggml_rms_norm(ctx.ctx, xt, 1e-5), wt)
-                outs = [L.ggml_mul_mat(ctx.ctx, w_, nm) for w_ in wts]
-                assert all(be.supports_op(o) for o in outs)
-                assert ctx.alloc(be)
-                gg.tensor_set(xt, x); gg.tensor_set(wt, wn.reshape(1, k))
-                for w_, (wb, _) in zip(wts, ws):
-                    gg.tensor_set(w_, wb)
-                be.compute(gg.graph_of(ctx, *outs))
-                res[fusion] = [gg.tensor_get(o)[0, 0, 0].copy() for o in outs]
-        finally:
-            be.set_option("fusion", 1)
-    for i, (_, wd) in enumerate(ws):
-        exp = (h @ wd.T)[0]
-        e1, e0 = nmse(exp, res[1][i]), nmse(exp, res[0][i])
-        print(f"{types} k={k} mat-vec {i}: NMSE fused {e1:.3g}, unfused {e0:.3g}")
-        assert e1 <= GATE and e0 <= GATE and nmse(res[0][i], res[1][i]) <= 5e-4
+    """same-format neighbours share one grouped launch (streamed at k % 256 == 0); a Q5_0 / Q5_1 pair, which has no common kernel, splits it"""
+    cases.check_mat_vecs_on_one_normed_activation(types, k, k + len(set(types)), None)
 
 
 @pytest.mark.parametrize("type_id,tname", [(3, "Q4_1"), (20, "IQ4_NL")])
 def test_other_32_element_formats_are_still_refused(type_id, tname):
-    """the backend has no kernel for them: supports_op says so and llama.cpp keeps those weights on the CPU"""
-    be = backend()
-    k, m, n_expert, n_used = 1024, 64, 4, 2
-    with gg.Context() as ctx:
-        for n in (1, 512):
-            assert not be.supports_op(L.ggml_mul_mat(ctx.ctx, ctx.new_tensor(type_id, [k, m]), ctx.new_tensor(gg.F32, [k, n]))), tname
-        op = L.ggml_mul_mat_id(ctx.ctx, ctx.new_tensor(type_id, [k, m, n_expert]), ctx.new_tensor(gg.F32, [k, n_used, 4]), ctx.new_tensor(gg.I32, [n_used, 4]))
-        assert not be.supports_op(op), tname
+    cases.check_other_32_element_formats_are_still_refused(type_id, tname)

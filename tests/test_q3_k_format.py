@@ -1,55 +1,15 @@
-"""Q3_K: this file's own numpy restatement of the block format against the golden vectors
+"""Q3_K: the numpy restatement of the block format (tests/weight_formats.py) against the golden vectors
 (tests/golden/make_golden_q3_k.py: the reference's gguf-py dequantize), bit for bit, and the C++ row decoder against the same.
 
-The oracle knows six formats and stays that way; tests/test_gpu_q3_k_weights.py builds its weights and its float64
-expectations with the functions below, so they are pinned here first (no GPU needed). gguf-py has no Q3_K quantizer, so
-weights are GENERATED blocks (random_q3_k): every byte random — which reaches every bit pattern, negative scales included —
-under a block scale of chosen magnitude.
-
-  Q3_K: 256 elements / 110 bytes: hmask 32 B | qs 64 B | scales 12 B | f16 d
-  element 128 n + 32 j + l:  q = ((qs[32 n + l] >> 2 j) & 3) - (bit 4 n + j of hmask[l] ? 0 : 4);  group g = element / 16
-  scale g: low four bits = nibble g / 8 of scales[g % 8], top two = bits 2 (g / 4) of scales[8 + g % 4], value sc - 32
-  x = (d * (sc_g - 32)) * q, in f32
+tests/gpu_weight_format_cases.py builds its Q3_K weights (generated blocks: random_q3_k) and its float64 expectations with those
+functions, so they are pinned here first (no GPU needed).
 """
 import numpy as np
 
-Q3_K = 11                               # enum ggml_type
-BLOCK_BYTES = 110
+from weight_formats import Q3_K, dequant_q3_k, random_q3_k, unpack_q3_k
+from weight_formats import BLOCK_BYTES as _BYTES
 
-
-def unpack_q3_k(blocks):
-    """blocks u8 [nb, 110] -> (q int32 [nb, 256] in -4..3, sc int32 [nb, 16] in -32..31, d f32 [nb, 1])"""
-    b = np.ascontiguousarray(blocks).reshape(-1, BLOCK_BYTES)
-    hmask, qs, scales = b[:, 0:32], b[:, 32:96], b[:, 96:108]
-    d = np.ascontiguousarray(b[:, 108:110]).view(np.float16).astype(np.float32)
-    q = np.empty((b.shape[0], 256), np.int32)
-    for n in range(2):
-        for j in range(4):
-            low = (qs[:, 32*n:32*n + 32] >> (2*j)) & 3
-            high = (hmask >> (4*n + j)) & 1
-            q[:, 128*n + 32*j:128*n + 32*j + 32] = low.astype(np.int32) - 4*(1 - high.astype(np.int32))
-    sc = np.empty((b.shape[0], 16), np.int32)
-    for g in range(16):
-        sc[:, g] = (((scales[:, g % 8] >> (4*(g // 8))) & 0xF) | (((scales[:, 8 + g % 4] >> (2*(g // 4))) & 3) << 4)).astype(np.int32) - 32
-    return q, sc, d
-
-
-def dequant_q3_k(blocks):
-    """blocks u8 [..., n*110] -> f32 [..., n*256]"""
-    q, sc, d = unpack_q3_k(blocks)
-    dl = (d * sc.astype(np.float32)).astype(np.float32)                     # [nb, 16]
-    x = (np.repeat(dl, 16, axis=1) * q.astype(np.float32)).astype(np.float32)
-    return x.reshape(*blocks.shape[:-1], -1)
-
-
-def random_q3_k(rng, shape, k, scale):
-    """valid Q3_K rows u8 [*shape, k/256*110]: every byte random, d = +-U(0.5, 2) * scale in f16"""
-    assert k % 256 == 0
-    nb = int(np.prod(shape, dtype=np.int64))*(k//256)
-    b = rng.integers(0, 256, size=(nb, BLOCK_BYTES), dtype=np.uint8)
-    d = (rng.uniform(0.5, 2.0, size=nb)*rng.choice([-1.0, 1.0], size=nb)*scale).astype(np.float16)
-    b[:, 108:110] = d.view(np.uint8).reshape(-1, 2)
-    return b.reshape(*shape, k//256*BLOCK_BYTES)
+BLOCK_BYTES = _BYTES[Q3_K]
 
 
 def _golden(golden_dir):

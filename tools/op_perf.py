@@ -2,7 +2,7 @@
 n in {1, 2, 3, 4, 5, 8, 512} — a Llama-3-8B ffn_down) plus the MoE cases (:6226-6229 shapes: MUL_MAT_ID 2880 x 2880, 32 experts top-4,
 and Mixtral's 8 experts top-2) through the backend's C-ABI. n <= 8 reports GB/s of weight bytes (memory-bound), n = 512 TFLOP/s.
 Wall clock over back-to-back graph computes (each case is its own one-node graph, as in test-backend-ops' perf mode).
-Q5_0 / Q5_1 (not in the oracle's six formats) are quantized by tests/test_q5_formats.py; Q3_K weights are tests/test_q3_k_format.py's generated blocks.
+Weights of every format come from tests/weight_formats.py (the oracle's generators for its six formats, numpy for Q5_0 / Q5_1 / Q3_K).
     op_perf.py OUT.json                      every case
     op_perf.py OUT.json --fa-only            only the FLASH_ATTN_EXT cases
     op_perf.py OUT.json --types=q5_0,q5_K    only the MUL_MAT cases of these formats"""
@@ -15,8 +15,7 @@ import numpy as np
 sys.path.insert(0, "tests"); sys.path.insert(0, "oracle"); sys.path.insert(0, ".")
 import oracle as orc
 from gpu_util import QTYPES, backend, gg
-from test_q5_formats import NAMES as Q5_NAMES, QUANT as Q5_QUANT
-from test_q3_k_format import random_q3_k
+from weight_formats import TYPES as MM_TYPES, weight_bytes
 
 L = gg.base(); be = backend()
 out = []
@@ -39,14 +38,11 @@ def timed(g, reps, windows=1):
 
 FA_ONLY = "--fa-only" in sys.argv[2:]
 ONLY_TYPES = [a.split("=", 1)[1].split(",") for a in sys.argv[2:] if a.startswith("--types=")]
-MM_TYPES = dict(QTYPES, q5_0=gg.Q5_0, q5_1=gg.Q5_1, q3_K=gg.Q3_K)
 
 for name in ([] if FA_ONLY else (ONLY_TYPES[0] if ONLY_TYPES else MM_TYPES)):
     m, k = 4096, 14336
     rng = np.random.default_rng(1234)
-    if name in Q5_NAMES: wb = Q5_QUANT[Q5_NAMES[name]](rng.uniform(-1, 1, size=(m, k)).astype(np.float32))
-    elif name == "q3_K": wb = random_q3_k(rng, (m,), k, 1/128)
-    else: wb = orc.random_blocks(rng, QTYPES[name], (m,), k)
+    wb = weight_bytes(rng, name, (m,), k)
     for n in (1, 2, 3, 4, 5, 8, 512):
         with gg.Context() as ctx:
             w = ctx.new_tensor(MM_TYPES[name], [k, m]); b = ctx.new_tensor(gg.F32, [k, n])
