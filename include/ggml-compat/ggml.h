@@ -362,6 +362,7 @@ GGML_API void ggml_set_output(struct ggml_tensor * tensor);
 GGML_API struct ggml_tensor * ggml_add     (struct ggml_context * ctx, struct ggml_tensor * a, struct ggml_tensor * b); // src/llama-model.cpp:6057
 GGML_API struct ggml_tensor * ggml_add_id  (struct ggml_context * ctx, struct ggml_tensor * a, struct ggml_tensor * b, struct ggml_tensor * ids); // src/llama-graph.cpp:927
 GGML_API struct ggml_tensor * ggml_mul     (struct ggml_context * ctx, struct ggml_tensor * a, struct ggml_tensor * b); // src/llama-graph.cpp:619
+GGML_API struct ggml_tensor * ggml_sub     (struct ggml_context * ctx, struct ggml_tensor * a, struct ggml_tensor * b);
 GGML_API struct ggml_tensor * ggml_div     (struct ggml_context * ctx, struct ggml_tensor * a, struct ggml_tensor * b); // src/llama-graph.cpp:910
 GGML_API struct ggml_tensor * ggml_sum_rows(struct ggml_context * ctx, struct ggml_tensor * a);                         // src/llama-graph.cpp:901
 GGML_API struct ggml_tensor * ggml_scale   (struct ggml_context * ctx, struct ggml_tensor * a, float s);
@@ -372,6 +373,8 @@ GGML_API void                 ggml_mul_mat_set_prec(struct ggml_tensor * a, enum
 GGML_API struct ggml_tensor * ggml_mul_mat_id(struct ggml_context * ctx, struct ggml_tensor * as, struct ggml_tensor * b, struct ggml_tensor * ids); // src/llama-graph.cpp:573
 GGML_API struct ggml_tensor * ggml_cpy     (struct ggml_context * ctx, struct ggml_tensor * a, struct ggml_tensor * b);
 GGML_API struct ggml_tensor * ggml_cont    (struct ggml_context * ctx, struct ggml_tensor * a);
+GGML_API struct ggml_tensor * ggml_dup     (struct ggml_context * ctx, struct ggml_tensor * a);
+GGML_API struct ggml_tensor * ggml_cont_4d (struct ggml_context * ctx, struct ggml_tensor * a, int64_t ne0, int64_t ne1, int64_t ne2, int64_t ne3);
 GGML_API struct ggml_tensor * ggml_cont_2d (struct ggml_context * ctx, struct ggml_tensor * a, int64_t ne0, int64_t ne1); // src/llama-graph.cpp:1330
 GGML_API struct ggml_tensor * ggml_reshape_2d(struct ggml_context * ctx, struct ggml_tensor * a, int64_t ne0, int64_t ne1);
 GGML_API struct ggml_tensor * ggml_reshape_3d(struct ggml_context * ctx, struct ggml_tensor * a, int64_t ne0, int64_t ne1, int64_t ne2);
@@ -400,6 +403,7 @@ GGML_API struct ggml_tensor * ggml_argsort (struct ggml_context * ctx, struct gg
 GGML_API struct ggml_tensor * ggml_top_k   (struct ggml_context * ctx, struct ggml_tensor * a, int k);                  // src/llama-graph.cpp:883
 GGML_API struct ggml_tensor * ggml_swiglu_split(struct ggml_context * ctx, struct ggml_tensor * a, struct ggml_tensor * b); // src/llama-graph.cpp:691
 GGML_API struct ggml_tensor * ggml_swiglu_oai(struct ggml_context * ctx, struct ggml_tensor * a, struct ggml_tensor * b, float alpha, float limit); // src/llama-graph.cpp:961
+GGML_API struct ggml_tensor * ggml_glu     (struct ggml_context * ctx, struct ggml_tensor * a, enum ggml_glu_op op, bool swapped);
 GGML_API struct ggml_tensor * ggml_glu_split(struct ggml_context * ctx, struct ggml_tensor * a, struct ggml_tensor * b, enum ggml_glu_op op);
 GGML_API struct ggml_tensor * ggml_unary   (struct ggml_context * ctx, struct ggml_tensor * a, enum ggml_unary_op op);
 GGML_API struct ggml_tensor * ggml_silu    (struct ggml_context * ctx, struct ggml_tensor * a);

@@ -383,6 +383,7 @@ static struct ggml_tensor * binop(struct ggml_context * ctx, enum ggml_op op, st
 struct ggml_tensor * ggml_add(struct ggml_context * ctx, struct ggml_tensor * a, struct ggml_tensor * b) { return binop(ctx, GGML_OP_ADD, a, b); }
 struct ggml_tensor * ggml_mul(struct ggml_context * ctx, struct ggml_tensor * a, struct ggml_tensor * b) { return binop(ctx, GGML_OP_MUL, a, b); }
 struct ggml_tensor * ggml_div(struct ggml_context * ctx, struct ggml_tensor * a, struct ggml_tensor * b) { return binop(ctx, GGML_OP_DIV, a, b); }
+struct ggml_tensor * ggml_sub(struct ggml_context * ctx, struct ggml_tensor * a, struct ggml_tensor * b) { return binop(ctx, GGML_OP_SUB, a, b); }
 
 // tests/test-backend-ops.cpp:2548 test_add_id
 struct ggml_tensor * ggml_add_id(struct ggml_context * ctx, struct ggml_tensor * a, struct ggml_tensor * b, struct ggml_tensor * ids) {
@@ -490,6 +491,18 @@ struct ggml_tensor * ggml_cont_2d(struct ggml_context * ctx, struct ggml_tensor 
     GGML_ASSERT(ggml_nelements(a) == ne0*ne1);
     ggml_tensor * r = ggml_new_tensor_2d(ctx, a->type, ne0, ne1);
     r->op = GGML_OP_CONT; r->src[0] = a;
+    return r;
+}
+struct ggml_tensor * ggml_cont_4d(struct ggml_context * ctx, struct ggml_tensor * a, int64_t ne0, int64_t ne1, int64_t ne2, int64_t ne3) {
+    GGML_ASSERT(ggml_nelements(a) == ne0*ne1*ne2*ne3);
+    ggml_tensor * r = ggml_new_tensor_4d(ctx, a->type, ne0, ne1, ne2, ne3);
+    r->op = GGML_OP_CONT; r->src[0] = a;
+    return r;
+}
+// tests/test-backend-ops.cpp:2383 test_dup
+struct ggml_tensor * ggml_dup(struct ggml_context * ctx, struct ggml_tensor * a) {
+    ggml_tensor * r = ggml_dup_tensor(ctx, a);
+    r->op = GGML_OP_DUP; r->src[0] = a;
     return r;
 }
 
@@ -655,6 +668,15 @@ struct ggml_tensor * ggml_glu_split(struct ggml_context * ctx, struct ggml_tenso
     ggml_tensor * r = ggml_new_tensor(ctx, a->type, GGML_MAX_DIMS, a->ne);
     r->op_params[0] = (int32_t) op; r->op_params[1] = 0; /* swapped */
     r->op = GGML_OP_GLU; r->src[0] = a; r->src[1] = b;
+    return r;
+}
+// the single-tensor form (tests/test-backend-ops.cpp:1832-1888): a holds [x | gate] along ne0 (swapped: [gate | x])
+struct ggml_tensor * ggml_glu(struct ggml_context * ctx, struct ggml_tensor * a, enum ggml_glu_op op, bool swapped) {
+    GGML_ASSERT(ggml_is_contiguous_1(a));
+    const int64_t ne[GGML_MAX_DIMS] = { a->ne[0]/2, a->ne[1], a->ne[2], a->ne[3] };
+    ggml_tensor * r = ggml_new_tensor(ctx, a->type, GGML_MAX_DIMS, ne);
+    r->op_params[0] = (int32_t) op; r->op_params[1] = swapped ? 1 : 0;
+    r->op = GGML_OP_GLU; r->src[0] = a; r->src[1] = NULL;
     return r;
 }
 struct ggml_tensor * ggml_swiglu_split(struct ggml_context * ctx, struct ggml_tensor * a, struct ggml_tensor * b) {

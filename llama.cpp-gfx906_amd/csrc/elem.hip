@@ -342,8 +342,14 @@ __global__ void __launch_bounds__(256) k_get_rows(const td src, const td idx, co
     if (i >= n) return;
     const idx4 ix = unravel(i, dst.ne0, dst.ne1, dst.ne2); const int64_t i0 = ix.i0, i10 = ix.i1, i11 = ix.i2, i12 = ix.i3;
     const int64_t r = *(const int32_t *) (idx.data + i10*idx.nb0 + i11*idx.nb1 + i12*idx.nb2);
-    const float v = ld_elem(src.data + i0*src.nb0 + r*src.nb1 + i11*src.nb2 + i12*src.nb3, src.type);
-    st_elem(dst.data + i0*dst.nb0 + i10*dst.nb1 + i11*dst.nb2 + i12*dst.nb3, dst.type, v);
+    const char * sp = src.data + i0*src.nb0 + r*src.nb1 + i11*src.nb2 + i12*src.nb3;
+    char * dp = dst.data + i0*dst.nb0 + i10*dst.nb1 + i11*dst.nb2 + i12*dst.nb3;
+    if (src.type == dst.type) {   // the bits, as k_cpy: an I32 source does not fit a float (16777217, INT32_MAX), and an F32 NaN keeps its payload
+        if (src.type == T_F32 || src.type == T_I32) *(uint32_t *) dp = *(const uint32_t *) sp;
+        else *(uint16_t *) dp = *(const uint16_t *) sp;
+    } else {
+        st_elem(dp, dst.type, ld_elem(sp, src.type));
+    }
 }
 void get_rows(const tensor_desc & src, const tensor_desc & idx, const tensor_desc & dst, hipStream_t stream) {
     const int64_t n = dst.ne[0]*dst.ne[1]*dst.ne[2]*dst.ne[3];
@@ -408,10 +414,13 @@ void argsort(const tensor_desc & src, const tensor_desc & dst, int order, hipStr
 
 // ---- UNARY — used by routers (sigmoid) and tests ----------------------------------------------------------
 enum { U_ABS, U_SGN, U_NEG, U_STEP, U_TANH, U_ELU, U_RELU, U_SIGMOID, U_GELU, U_GELU_QUICK, U_SILU, U_HARDSWISH, U_HARDSIGMOID, U_EXP, U_GELU_ERF };
+// tanh form. 0.5*(1 + tanh(u)) is written as 1/(1 + exp(-2u)), the same function: below x = -4 the sum 1 + tanhf(u) keeps one or two bits
+// (an F16 / BF16 result there was up to thousands of ulps off); gelu_erf_f likewise takes 1 + erf(z) as erfc(-z)
 static __device__ __forceinline__ float gelu_f(float x) {
     const float c = 0.044715f, s = 0.79788456080286535587989211986876f;
-    return 0.5f*x*(1.0f + tanhf(s*x*(1.0f + c*x*x)));
+    return x/(1.0f + expf(-2.0f*(s*x*(1.0f + c*x*x))));
 }
+static __device__ __forceinline__ float gelu_erf_f(float x) { return 0.5f*x*erfcf(-x*0.70710678118654752440f); }
 static __device__ __forceinline__ float silu_f(float x) { return x/(1.0f + expf(-x)); }
 __global__ void __launch_bounds__(256) k_unary(int op, const td src, const td dst, int64_t n) {
     const int64_t i = (int64_t) blockIdx.x*256 + threadIdx.x;
@@ -434,7 +443,7 @@ __global__ void __launch_bounds__(256) k_unary(int op, const td src, const td ds
         case U_HARDSWISH: r = x*fminf(1.0f, fmaxf(0.0f, (x + 3.0f)/6.0f)); break;
         case U_HARDSIGMOID: r = fminf(1.0f, fmaxf(0.0f, (x + 3.0f)/6.0f)); break;
         case U_EXP: r = expf(x); break;
-        case U_GELU_ERF: r = 0.5f*x*(1.0f + erff(x*0.70710678118654752440f)); break;
+        case U_GELU_ERF: r = gelu_erf_f(x); break;
         default: r = x; break;
     }
     st_elem(dst.data + i0*dst.nb0 + i1*dst.nb1 + i2*dst.nb2 + i3*dst.nb3, dst.type, r);
@@ -464,7 +473,7 @@ __global__ void __launch_bounds__(256) k_glu(int op, const td a, const td b, con
             const float gc = fmaxf(fminf(g, limit), -limit);
             r = (xc/(1.0f + expf(-xc*alpha)))*(gc + 1.0f);
         } break;
-        case G_GEGLU_ERF: r = 0.5f*x*(1.0f + erff(x*0.70710678118654752440f))*g; break;
+        case G_GEGLU_ERF: r = gelu_erf_f(x)*g; break;
         case G_GEGLU_QUICK: r = x*(1.0f/(1.0f + expf(-1.702f*x)))*g; break;
         default: r = 0.f; break;
     }

@@ -24,13 +24,13 @@ GGML_MAX_DIMS, GGML_MAX_SRC, GGML_MAX_NAME, GGML_MAX_OP_PARAMS = 4, 10, 64, 64
 F32, F16, Q4_0, Q8_0, Q4_K, Q5_K, Q6_K, Q8_K, I32, I64, BF16, MXFP4 = 0, 1, 2, 8, 12, 13, 14, 15, 26, 27, 30, 39
 Q5_0, Q5_1 = 6, 7
 Q3_K = 11
-TYPE_NP = {F32: np.float32, F16: np.float16, I32: np.int32, I64: np.int64}
+TYPE_NP = {F32: np.float32, F16: np.float16, I32: np.int32, I64: np.int64, BF16: np.uint16}      # BF16 travels as its 16 bits
 # (block size, type size) — gguf-py/gguf/constants.py:2839-2872
 QUANT_SIZES = {F32: (1, 4), F16: (1, 2), BF16: (1, 2), I32: (1, 4), I64: (1, 8), Q4_0: (32, 18), Q5_0: (32, 22), Q5_1: (32, 24), Q8_0: (32, 34),
                Q3_K: (256, 110), Q4_K: (256, 144), Q5_K: (256, 176), Q6_K: (256, 210), MXFP4: (32, 17)}
 
 GGML_STATUS_SUCCESS = 0
-GGML_ROPE_TYPE_NEOX = 2
+GGML_ROPE_TYPE_NEOX, GGML_ROPE_TYPE_MROPE, GGML_ROPE_TYPE_VISION = 2, 8, 24
 GGML_SORT_ORDER_ASC, GGML_SORT_ORDER_DESC = 0, 1
 (GLU_REGLU, GLU_GEGLU, GLU_SWIGLU, GLU_SWIGLU_OAI, GLU_GEGLU_ERF, GLU_GEGLU_QUICK) = range(6)
 (UNARY_ABS, UNARY_SGN, UNARY_NEG, UNARY_STEP, UNARY_TANH, UNARY_ELU, UNARY_RELU, UNARY_SIGMOID, UNARY_GELU,
@@ -121,16 +121,16 @@ def base():
     _sig(L, "ggml_new_tensor_4d", T, [vp, ci, i64, i64, i64, i64])
     _sig(L, "ggml_nbytes", sz, [T]); _sig(L, "ggml_nelements", i64, [T])
     _sig(L, "ggml_set_name", T, [T, C.c_char_p])
-    for n in ("ggml_add", "ggml_mul", "ggml_div", "ggml_mul_mat", "ggml_get_rows", "ggml_cpy", "ggml_swiglu_split"):
+    for n in ("ggml_add", "ggml_sub", "ggml_mul", "ggml_div", "ggml_mul_mat", "ggml_get_rows", "ggml_cpy", "ggml_swiglu_split"):
         _sig(L, n, T, [vp, T, T])
     for n in ("ggml_add_id", "ggml_mul_mat_id", "ggml_set_rows"):
         _sig(L, n, T, [vp, T, T, T])
-    for n in ("ggml_sum_rows", "ggml_cont", "ggml_transpose", "ggml_soft_max", "ggml_silu", "ggml_sigmoid"):
+    for n in ("ggml_sum_rows", "ggml_cont", "ggml_dup", "ggml_transpose", "ggml_soft_max", "ggml_silu", "ggml_sigmoid"):
         _sig(L, n, T, [vp, T])
     _sig(L, "ggml_scale", T, [vp, T, cf]); _sig(L, "ggml_scale_bias", T, [vp, T, cf, cf])
     _sig(L, "ggml_rms_norm", T, [vp, T, cf])
     _sig(L, "ggml_mul_mat_set_prec", None, [T, ci])
-    _sig(L, "ggml_cont_2d", T, [vp, T, i64, i64])
+    _sig(L, "ggml_cont_2d", T, [vp, T, i64, i64]); _sig(L, "ggml_cont_4d", T, [vp, T, i64, i64, i64, i64])
     _sig(L, "ggml_reshape_2d", T, [vp, T, i64, i64]); _sig(L, "ggml_reshape_3d", T, [vp, T, i64, i64, i64])
     _sig(L, "ggml_reshape_4d", T, [vp, T, i64, i64, i64, i64])
     _sig(L, "ggml_view_1d", T, [vp, T, i64, sz]); _sig(L, "ggml_view_2d", T, [vp, T, i64, i64, sz, sz])
@@ -143,6 +143,7 @@ def base():
     _sig(L, "ggml_rope_ext", T, [vp, T, T, T, ci, ci, ci, cf, cf, cf, cf, cf, cf])
     _sig(L, "ggml_argsort", T, [vp, T, ci]); _sig(L, "ggml_top_k", T, [vp, T, ci])
     _sig(L, "ggml_swiglu_oai", T, [vp, T, T, cf, cf]); _sig(L, "ggml_glu_split", T, [vp, T, T, ci])
+    _sig(L, "ggml_glu", T, [vp, T, ci, C.c_bool])
     _sig(L, "ggml_unary", T, [vp, T, ci])
     _sig(L, "ggml_new_graph_custom", vp, [vp, sz, C.c_bool]); _sig(L, "ggml_build_forward_expand", None, [vp, T])
     _sig(L, "ggml_graph_n_nodes", ci, [vp]); _sig(L, "ggml_graph_node", T, [vp, ci])
@@ -340,6 +341,23 @@ def tensor_get(t) -> np.ndarray:
         return raw.view(TYPE_NP[tt.type]).reshape(shape + (tt.ne[0],))
     bs, ts = QUANT_SIZES[tt.type]
     return raw.reshape(shape + (tt.ne[0] // bs * ts,))
+
+
+def tensor_get_strided(t) -> np.ndarray:
+    """any view (permuted, strided, offset) of an unquantized tensor: reads the PARENT tensor whole and returns it together with the
+    view's elements, shaped [ne3, ne2, ne1, ne0] -> (view elements, parent array). The parent is what a test compares byte for byte when
+    an op writes into a view."""
+    tt = t.contents
+    par = tt.view_src if tt.view_src else t
+    whole = tensor_get(par)
+    dt = TYPE_NP[tt.type]
+    flat = np.ascontiguousarray(whole).reshape(-1).view(np.uint8)
+    span = base().ggml_nbytes(t)
+    off = tt.view_offs if tt.view_src else 0
+    assert off + span <= flat.nbytes, "view reaches past its parent"
+    v = np.lib.stride_tricks.as_strided(np.frombuffer(flat.data, dtype=dt, count=span // dt().itemsize, offset=off),
+                                        shape=(tt.ne[3], tt.ne[2], tt.ne[1], tt.ne[0]), strides=(tt.nb[3], tt.nb[2], tt.nb[1], tt.nb[0]))
+    return v.copy(), whole
 
 
 def graph_of(ctx: Context, *outs, size=8192):

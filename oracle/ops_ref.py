@@ -183,3 +183,144 @@ def flash_attn_ext(q, K, V, mask, scale, max_bias=0.0, softcap=0.0, sinks=None):
         p = np.exp(s - mx); den = p.sum(-1, keepdims=True) + (np.exp(sinks[h] - mx) if sinks is not None else 0.0)
         out[:, h, :] = (p / den) @ V[:, hk, :]
     return out
+
+
+# ---- element ops beyond the decode path: every variant supports_op accepts (tests/test_gpu_elem_ops.py) ----------------------------
+def _f64(x):
+    return np.asarray(x, dtype=np.float64)
+
+
+# The tables keep the dtype they are given: float64 for the reference; float32 to ask, on the CPU, how far a float32 evaluation of the
+# same formula lands from it. The GELU forms are written without the cancellation of 1 + tanh(u) and 1 + erf(z) in the negative tail:
+# 0.5 * (1 + tanh(u)) = 1 / (1 + exp(-2u)) and 1 + erf(z) = erfc(-z), the same functions.
+_erfc = np.vectorize(math.erfc, otypes=[np.float64])
+
+
+def _sigmoid(x):
+    with np.errstate(over="ignore"):
+        return 1.0 / (1.0 + np.exp(-x))
+
+
+def _gelu_tanh(x):
+    return x * _sigmoid(2.0 * (0.79788456080286535587989211986876 * x * (1.0 + 0.044715 * x * x)))
+
+
+def _gelu_erf(x):
+    return 0.5 * x * _erfc(-x * 0.70710678118654752440).astype(x.dtype)
+
+
+def _hardsigmoid(x):
+    return np.minimum(1.0, np.maximum(0.0, (x + 3.0) / 6.0))
+
+
+def _swiglu_oai(x, g, alpha=1.702, limit=7.0):
+    xc = np.minimum(x, limit)
+    return (xc * _sigmoid(xc * alpha)) * (np.clip(g, -limit, limit) + 1.0)
+
+
+# enum ggml_unary_op order (ABS ... GELU_ERF) -> f(x), from the mathematical definitions; GELU is the tanh form with elem.hip's constants
+UNARY = {
+    0: np.abs,
+    1: lambda x: np.where(x > 0, 1.0, np.where(x < 0, -1.0, 0.0)).astype(x.dtype),
+    2: lambda x: -x,
+    3: lambda x: (x > 0).astype(x.dtype),
+    4: np.tanh,
+    5: lambda x: np.where(x > 0, x, np.expm1(np.minimum(x, 0.0))),
+    6: lambda x: np.where(x > 0, x, 0.0).astype(x.dtype),
+    7: _sigmoid,
+    8: _gelu_tanh,
+    9: lambda x: x * _sigmoid(1.702 * x),
+    10: lambda x: x * _sigmoid(x),
+    11: lambda x: x * _hardsigmoid(x),
+    12: _hardsigmoid,
+    13: np.exp,
+    14: _gelu_erf,
+}
+UNARY_NAMES = ["abs", "sgn", "neg", "step", "tanh", "elu", "relu", "sigmoid", "gelu", "gelu_quick", "silu", "hardswish", "hardsigmoid", "exp", "gelu_erf"]
+
+
+# enum ggml_glu_op order (REGLU, GEGLU, SWIGLU, SWIGLU_OAI, GEGLU_ERF, GEGLU_QUICK) -> f(x, g): act(x) * g (SWIGLU_OAI: alpha 1.702, limit 7)
+GLU = {
+    0: lambda x, g: np.maximum(x, 0.0) * g,
+    1: lambda x, g: _gelu_tanh(x) * g,
+    2: lambda x, g: x * _sigmoid(x) * g,
+    3: _swiglu_oai,
+    4: lambda x, g: _gelu_erf(x) * g,
+    5: lambda x, g: x * _sigmoid(1.702 * x) * g,
+}
+GLU_NAMES = ["reglu", "geglu", "swiglu", "swiglu_oai", "geglu_erf", "geglu_quick"]
+
+
+def sub(a, b):
+    """a - repeat(b) in float64 (tests/test-backend-ops.cpp:2469)"""
+    return _f64(a) - bcast(_f64(b), a.shape)
+
+
+def argsort(x, order):
+    """tests/test-backend-ops.cpp:4120 — order 0 ascending, 1 descending"""
+    return np.argsort(x if order == 0 else -x, axis=-1, kind="stable").astype(np.int32)
+
+
+def get_rows_batched(src, idx):
+    """tests/test-backend-ops.cpp:1951 — src [ne3, ne2, rows, ne0], idx [ne12, ne11, ne10] with ne11 = ne2, ne12 = ne3 -> [ne12, ne11, ne10, ne0];
+    the values are moved, not computed: the result keeps src's dtype"""
+    n12, n11, n10 = idx.shape
+    out = np.empty((n12, n11, n10, src.shape[-1]), dtype=src.dtype)
+    for i12 in range(n12):
+        for i11 in range(n11):
+            out[i12, i11] = src[i12, i11][idx[i12, i11]]
+    return out
+
+
+def set_rows_bcast(dst, src, idx, conv):
+    """tests/test-backend-ops.cpp:2060-2127 — dst [ne3, ne2, rows, ne0] (storage dtype), src f32 [ne3, ne2, ne1, ne0], idx i64 [ne12, ne11, ne1]
+    broadcast over (i2 % ne11, i3 % ne12); conv rounds a float32 row to dst's storage"""
+    out = dst.copy()
+    n3, n2, n1, _ = src.shape
+    for i3 in range(n3):
+        for i2 in range(n2):
+            out[i3, i2, idx[i3 % idx.shape[0], i2 % idx.shape[1]]] = conv(src[i3, i2])
+    return out
+
+
+def cpy(src_view, dst_shape):
+    """tests/test-backend-ops.cpp:2438 — element i of src (in src's logical order) becomes element i of dst (in dst's logical order)"""
+    return np.ascontiguousarray(src_view).reshape(dst_shape)
+
+
+def round_f16(x):
+    """float -> IEEE binary16, round to nearest even (one rounding, also from float64)"""
+    with np.errstate(over="ignore"):
+        return np.asarray(x).astype(np.float16)
+
+
+def round_bf16(x):
+    """float32 -> bf16 bits (uint16): round to nearest even on the upper 16 bits; NaN stays NaN with the quiet bit set
+    (ggml_compute_fp32_to_bf16's rule, restated in elem.hip st_elem)"""
+    u = np.ascontiguousarray(x, dtype=np.float32).view(np.uint32)
+    nan = (u & np.uint32(0x7FFFFFFF)) > np.uint32(0x7F800000)
+    r = (u.astype(np.uint64) + np.uint64(0x7FFF) + ((u >> np.uint32(16)) & np.uint32(1)).astype(np.uint64)) >> np.uint64(16)
+    return np.where(nan, (u >> np.uint32(16)) | np.uint32(64), r).astype(np.uint16)
+
+
+def bf16_to_f32(h):
+    return (np.asarray(h, dtype=np.uint16).astype(np.uint32) << np.uint32(16)).view(np.float32)
+
+
+def round_bf16_from_f64(x):
+    """float64 -> bf16 bits with ONE rounding (through float32 would round twice): the two bf16 neighbours of the float32 image are
+    compared with x in float64 (their differences are exact), ties to the even mantissa"""
+    x = _f64(x)
+    with np.errstate(over="ignore"):
+        u = np.ascontiguousarray(x.astype(np.float32)).view(np.uint32)
+    lo = u & np.uint32(0xFFFF0000)
+    hi = lo + np.uint32(0x10000)
+    with np.errstate(invalid="ignore"):
+        flo, fhi = lo.view(np.float32).astype(np.float64), hi.view(np.float32).astype(np.float64)
+    fhi = np.where(np.isinf(fhi), np.copysign(2.0 ** 128, fhi), fhi)       # the neighbour above the largest finite bf16 stands for infinity
+    with np.errstate(invalid="ignore"):
+        dlo, dhi = np.abs(x - flo), np.abs(fhi - x)
+    up = (dhi < dlo) | ((dhi == dlo) & (((lo >> np.uint32(16)) & np.uint32(1)) == 1))
+    out = np.where(up, hi, lo) >> np.uint32(16)
+    special = ~np.isfinite(x)
+    return np.where(special, round_bf16(x.astype(np.float32)), out).astype(np.uint16)
