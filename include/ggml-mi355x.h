@@ -76,6 +76,13 @@ struct ggml_backend_mi355x_counters {
     uint64_t graph_partial_replays;  // graph_compute calls that launched a cached graph's leading segments and then the rest: eagerly, or from the
                                      // segments of this graph's own entry (captured then, or earlier) that begin where the matched prefix ends
     uint64_t moe_combine_direct;     // MoE combines that took their routing weights from the fused router's hand-off (moe_ws) instead of the probabilities
+    // dense (F16 / BF16 / F32 src0) MUL_MATs by the kernel that ran them (mm_dense.hip: mul_mat_dense_path), and dense MUL_MAT_IDs
+    uint64_t dense_mfma;             // k_act_to_16 + k_mmq<T_F16>
+    uint64_t dense_f16_pairs;        // k_mm_dense<8, 1>
+    uint64_t dense_f32_vec;          // k_mm_dense<8, 2>
+    uint64_t dense_f32_rows;         // k_mm_dense_rows<8, 4> (m >= 32) or <8, 2>
+    uint64_t dense_generic;          // k_mm_dense<8, 0>
+    uint64_t dense_id;               // k_mm_id_dense
 };
 // Row-split weights (-sm row). Replaces ggml_backend_cuda_split_buffer_type, which the host finds through the registry proc
 // "ggml_backend_split_buffer_type" (src/llama-model.cpp:368-387; typedef ggml_backend_split_buffer_type_t, ggml-backend.h): main_device is

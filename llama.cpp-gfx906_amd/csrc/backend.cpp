@@ -478,7 +478,7 @@ static bool mi_supports_op(const struct ggml_tensor * op) {
         case GGML_OP_MUL_MAT_ID: {
             if (op->type != GGML_TYPE_F32 || s1->type != GGML_TYPE_F32) return false;
             if (s0->type == GGML_TYPE_F16 || s0->type == GGML_TYPE_F32 || s0->type == GGML_TYPE_BF16)      // an unquantized expert stack (tests/test-backend-ops.cpp:5821-5824)
-                return op->src[2]->type == GGML_TYPE_I32 && op->nb[0] == 4;
+                return op->src[2]->type == GGML_TYPE_I32 && op->nb[0] == 4 && op->src[2]->ne[0] <= 65535 && op->src[2]->ne[1] <= 65535;      // (k_mm_id_dense: slots and tokens are grid dims y and z)
             if (!ggml_is_quantized(s0->type) || !mul_mat_vec_q_supported((int) s0->type)) return false;
             if (s0->ne[0] % ggml_blck_size(s0->type) != 0) return false;
             if (s1->nb[0] != sizeof(float)) return false;

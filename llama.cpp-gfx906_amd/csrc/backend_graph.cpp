@@ -28,8 +28,11 @@ static size_t graph_scratch_need(const struct ggml_cgraph * g) {
                 }
             }
             if (s > need) need = s;
-        } else if (n->op == GGML_OP_MUL_MAT && n->src[0]->type == GGML_TYPE_F16 && n->src[1]->type == GGML_TYPE_F32 && n->src[1]->ne[1] > MMVQ_MAX_N) {
-            const size_t s = (size_t)((n->src[1]->ne[0] + 63) & ~(int64_t) 63)*(size_t) ggml_nrows(n->src[1])*2 + 1024;     // f16 copy of src1 (rows padded to 64) for the matrix-core attention products
+        } else if (n->op == GGML_OP_MUL_MAT && !ggml_is_quantized(n->src[0]->type)) {
+            // the matrix-core attention products: the f16 copy of src1, where and as large as mul_mat_dense_path asks for it — so that path is taken
+            // from a backend's first graph on, whatever ran before, and nothing is requested for a product another kernel runs
+            const mm_dense_args p = mm_dense_args_of(n);
+            const size_t s = mul_mat_dense_mfma_supported(p) ? mul_mat_dense_mfma_scratch_bytes(p) : 0;
             if (s > need) need = s;
         }
     }

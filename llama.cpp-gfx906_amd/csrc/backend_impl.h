@@ -219,6 +219,19 @@ static inline tensor_desc desc(const struct ggml_tensor * t) {
     for (int i = 0; i < 4; i++) { d.ne[i] = t->ne[i]; d.nb[i] = t->nb[i]; }
     return d;
 }
+// the arguments of a dense (F16 / BF16 / F32 src0) MUL_MAT node: what mul_mat_dense_path decides from, for the launch and for the graph's scratch request alike
+static inline mm_dense_args mm_dense_args_of(const struct ggml_tensor * dst) {
+    const struct ggml_tensor * a = dst->src[0]; const struct ggml_tensor * b = dst->src[1];
+    mm_dense_args p;
+    p.a = a->data; p.type_a = (int) a->type;
+    p.ne00 = a->ne[0]; p.ne01 = a->ne[1]; p.ne02 = a->ne[2]; p.ne03 = a->ne[3];
+    p.nb00 = a->nb[0]; p.nb01 = a->nb[1]; p.nb02 = a->nb[2]; p.nb03 = a->nb[3];
+    p.b = b->data; p.type_b = (int) b->type;
+    p.ne10 = b->ne[0]; p.ne11 = b->ne[1]; p.ne12 = b->ne[2]; p.ne13 = b->ne[3];
+    p.nb10 = b->nb[0]; p.nb11 = b->nb[1]; p.nb12 = b->nb[2]; p.nb13 = b->nb[3];
+    p.dst = (float *) dst->data; p.nb1 = dst->nb[1]; p.nb2 = dst->nb[2]; p.nb3 = dst->nb[3];
+    return p;
+}
 static inline bool ranges_overlap(const void * a, size_t na, const void * b, size_t nb) {
     const char * pa = (const char *) a; const char * pb = (const char *) b;
     return pa < pb + nb && pb < pa + na;

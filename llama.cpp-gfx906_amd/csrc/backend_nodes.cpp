@@ -149,22 +149,16 @@ static void op_mul_mat(mi_backend_ctx * c, struct ggml_tensor * dst, struct ggml
         }
         return;
     }
-    mm_dense_args p;
-    p.a = a->data; p.type_a = (int) a->type;
-    p.ne00 = a->ne[0]; p.ne01 = a->ne[1]; p.ne02 = a->ne[2]; p.ne03 = a->ne[3];
-    p.nb00 = a->nb[0]; p.nb01 = a->nb[1]; p.nb02 = a->nb[2]; p.nb03 = a->nb[3];
-    p.b = b->data; p.type_b = (int) b->type;
-    p.ne10 = b->ne[0]; p.ne11 = b->ne[1]; p.ne12 = b->ne[2]; p.ne13 = b->ne[3];
-    p.nb10 = b->nb[0]; p.nb11 = b->nb[1]; p.nb12 = b->nb[2]; p.nb13 = b->nb[3];
-    p.dst = (float *) dst->data; p.nb1 = dst->nb[1]; p.nb2 = dst->nb[2]; p.nb3 = dst->nb[3];
-    if (mul_mat_dense_mfma_supported(p) && mul_mat_dense_mfma_scratch_bytes(p) <= c->scratch_size) {
-        c->pass.drop_act();   // scratch reused
-        mul_mat_dense_mfma(p, c->scratch, c->stream);
-        c->cnt.kernels_launched += 2;
-        return;
+    const mm_dense_args p = mm_dense_args_of(dst);
+    int launches = 0;
+    switch (mul_mat_dense(p, c->scratch, c->scratch_size, c->stream, &launches)) {
+        case MM_DENSE_MFMA:      c->pass.drop_act(); c->cnt.dense_mfma++; break;      // (the scratch was reused)
+        case MM_DENSE_F16_PAIRS: c->cnt.dense_f16_pairs++; break;
+        case MM_DENSE_F32_VEC:   c->cnt.dense_f32_vec++; break;
+        case MM_DENSE_F32_ROWS:  c->cnt.dense_f32_rows++; break;
+        case MM_DENSE_GENERIC:   c->cnt.dense_generic++; break;
     }
-    mul_mat_dense(p, c->stream);
-    c->cnt.kernels_launched++;
+    c->cnt.kernels_launched += (uint64_t) launches;
 }
 
 // MUL_MAT on a row-split weight: the main device quantizes the activations once (few tokens) and runs its own slice; every other device that holds
@@ -226,7 +220,7 @@ static void op_mul_mat_id(mi_backend_ctx * c, struct ggml_tensor * dst) {
     if (!ggml_is_quantized(as->type)) {      // F16 / BF16 / F32 expert stack
         mul_mat_id_dense((int) as->type, as->data, as->nb[0], as->nb[1], as->nb[2], M, K, b->data, b->nb[0], b->nb[1], b->nb[2], n_b,
                          ids->data, ids->nb[0], ids->nb[1], n_used, n_tokens, as->ne[2], (float *) dst->data, dst->nb[1], dst->nb[2], c->stream);
-        c->cnt.kernels_launched++;
+        c->cnt.kernels_launched++; c->cnt.dense_id++;
         return;
     }
     const int kind = act_kind_for((int) as->type);

@@ -134,7 +134,10 @@ struct mm_dense_args {
     const void * b; int type_b; int64_t ne10, ne11, ne12, ne13; size_t nb10, nb11, nb12, nb13;
     float * dst; size_t nb1, nb2, nb3;
 };
-void mul_mat_dense(const mm_dense_args & p, hipStream_t stream);
+// the kernel a dense MUL_MAT runs (mm_dense.hip: mul_mat_dense_path decides, from the arguments and the scratch size alone; mul_mat_dense launches it and says which)
+enum mm_dense_path { MM_DENSE_MFMA, MM_DENSE_F16_PAIRS, MM_DENSE_F32_VEC, MM_DENSE_F32_ROWS, MM_DENSE_GENERIC };
+mm_dense_path mul_mat_dense_path(const mm_dense_args & p, size_t scratch_bytes);
+mm_dense_path mul_mat_dense(const mm_dense_args & p, void * scratch, size_t scratch_bytes, hipStream_t stream, int * n_launches);      // n_launches: how many kernels it started
 // MUL_MAT_ID over an F16 / BF16 / F32 expert stack (correctness path: a wave per (row, pair))
 void mul_mat_id_dense(int type_a, const void * as, size_t nb00, size_t nb01, size_t nb02, int64_t m, int64_t k, const void * b, size_t nb10, size_t nb11, size_t nb12, int64_t n_b,
                       const void * ids, size_t ids_nb0, size_t ids_nb1, int64_t n_used, int64_t n_tokens, int64_t n_expert, float * dst, size_t nb1, size_t nb2, hipStream_t stream);

@@ -10,6 +10,8 @@
 #include "dev_common.h"
 #include "kernels.h"
 
+#include <algorithm>
+
 namespace mi355x {
 
 static __device__ __forceinline__ float ld_a(const char * p, int type) {
@@ -20,12 +22,13 @@ static __device__ __forceinline__ float ld_a(const char * p, int type) {
 
 template <int NC, int FAST>   // FAST 1: a contiguous f16 along k, b contiguous f32 along k; FAST 2: both contiguous f32, 16-byte aligned rows
                                // (the MoE router: F32 [n_embd, n_expert] x the normed activation, src/llama-graph.cpp:838)
-__global__ void __launch_bounds__(256) k_mm_dense(const mm_dense_args p) {
+__global__ void __launch_bounds__(256) k_mm_dense(const mm_dense_args p, const int64_t y0, const int64_t z0) {   // (y0, z0): where this launch's grid starts, see mul_mat_dense
     const int lane = threadIdx.x & 63;
     const int64_t i01 = (int64_t) blockIdx.x*4 + (threadIdx.x >> 6);
     if (i01 >= p.ne01) return;
-    const int64_t c0 = (int64_t) blockIdx.y*NC;
-    const int64_t i12 = blockIdx.z % p.ne12, i13 = blockIdx.z / p.ne12;
+    const int64_t c0 = (y0 + blockIdx.y)*NC;
+    const int64_t bz = z0 + blockIdx.z;
+    const int64_t i12 = bz % p.ne12, i13 = bz / p.ne12;
     const int64_t i02 = i12/(p.ne12/p.ne02), i03 = i13/(p.ne13/p.ne03);
     const char * a = (const char *) p.a + i01*p.nb01 + i02*p.nb02 + i03*p.nb03;
     const char * b = (const char *) p.b + i12*p.nb12 + i13*p.nb13;
@@ -88,12 +91,13 @@ __global__ void __launch_bounds__(256) k_mm_dense(const mm_dense_args p) {
 // is NR + NC loads for NR*NC*4 multiply-adds instead of 1 + NC for NC*4 — the same per-lane k assignment, expression and reduction as k_mm_dense<NC, 2>, hence the
 // same bits (the router's logits decide the routing: nothing is rounded differently from the one-token path)
 template <int NC, int NR>
-__global__ void __launch_bounds__(256) k_mm_dense_rows(const mm_dense_args p) {
+__global__ void __launch_bounds__(256) k_mm_dense_rows(const mm_dense_args p, const int64_t y0, const int64_t z0) {
     const int lane = threadIdx.x & 63;
     const int64_t r0 = ((int64_t) blockIdx.x*4 + (threadIdx.x >> 6))*NR;
     if (r0 >= p.ne01) return;
-    const int64_t c0 = (int64_t) blockIdx.y*NC;
-    const int64_t i12 = blockIdx.z % p.ne12, i13 = blockIdx.z / p.ne12;
+    const int64_t c0 = (y0 + blockIdx.y)*NC;
+    const int64_t bz = z0 + blockIdx.z;
+    const int64_t i12 = bz % p.ne12, i13 = bz / p.ne12;
     const int64_t i02 = i12/(p.ne12/p.ne02), i03 = i13/(p.ne13/p.ne03);
     const char * a = (const char *) p.a + i02*p.nb02 + i03*p.nb03;
     const char * b = (const char *) p.b + i12*p.nb12 + i13*p.nb13;
@@ -123,24 +127,55 @@ __global__ void __launch_bounds__(256) k_mm_dense_rows(const mm_dense_args p) {
         }
 }
 
-void mul_mat_dense(const mm_dense_args & p, hipStream_t stream) {
-    if (p.ne01 == 0 || p.ne11 == 0 || p.ne12*p.ne13 == 0) return;
-    const bool fast = p.type_a == T_F16 && p.type_b == T_F32 && p.nb00 == 2 && p.nb10 == 4 && (p.ne00 % 2 == 0);
-    constexpr int NC = 8;
-    const dim3 grid((unsigned)((p.ne01 + 3)/4), (unsigned)((p.ne11 + NC - 1)/NC), (unsigned)(p.ne12*p.ne13));
+// ---- which kernel a dense MUL_MAT runs: decided here, once, from the shapes, strides and addresses alone; mul_mat_dense launches what this says ----
+//   MFMA       k_act_to_16<true> + k_mmq<T_F16> (mmq.hip): F16 x F32, both contiguous along k, n > 8, k % 32 == 0, the f16 copy of b fits the scratch
+//   F16 pairs  k_mm_dense<8, 1>: F16 x F32, both contiguous along k, k even
+//   F32 rows   k_mm_dense_rows<8, 4 | 2>: F32 x F32, k % 4 == 0, every row 16-byte aligned, n >= 64 and m >= 32 | 8 <= m < 32
+//   F32 vec    k_mm_dense<8, 2>: the same operands with fewer columns or rows
+//   generic    k_mm_dense<8, 0>: everything else supports_op accepts (BF16, F16 src1, odd k, nb00 / nb10 that is not the element size, unaligned F32 rows)
+mm_dense_path mul_mat_dense_path(const mm_dense_args & p, size_t scratch_bytes) {
+    if (mul_mat_dense_mfma_supported(p) && mul_mat_dense_mfma_scratch_bytes(p) <= scratch_bytes) return MM_DENSE_MFMA;
+    if (p.type_a == T_F16 && p.type_b == T_F32 && p.nb00 == 2 && p.nb10 == 4 && (p.ne00 % 2 == 0)) return MM_DENSE_F16_PAIRS;
     const bool fast32 = p.type_a == T_F32 && p.type_b == T_F32 && p.nb00 == 4 && p.nb10 == 4 && p.ne00 % 4 == 0 && p.ne00 < (1ll << 30) &&
                         ((uintptr_t) p.a % 16) == 0 && ((uintptr_t) p.b % 16) == 0 && p.nb01 % 16 == 0 && p.nb02 % 16 == 0 && p.nb03 % 16 == 0 &&
                         p.nb11 % 16 == 0 && p.nb12 % 16 == 0 && p.nb13 % 16 == 0;
-    if (fast)        hipLaunchKernelGGL((k_mm_dense<NC, 1>), grid, dim3(256), 0, stream, p);
-    else if (fast32 && p.ne11 >= 64 && p.ne01 >= 32) {
-        const dim3 g4((unsigned)((p.ne01 + 15)/16), (unsigned)((p.ne11 + NC - 1)/NC), (unsigned)(p.ne12*p.ne13));
-        hipLaunchKernelGGL((k_mm_dense_rows<NC, 4>), g4, dim3(256), 0, stream, p);
-    } else if (fast32 && p.ne11 >= 64 && p.ne01 >= 8) {      // (few experts: two rows per wave keep enough waves in flight)
-        const dim3 g2((unsigned)((p.ne01 + 7)/8), (unsigned)((p.ne11 + NC - 1)/NC), (unsigned)(p.ne12*p.ne13));
-        hipLaunchKernelGGL((k_mm_dense_rows<NC, 2>), g2, dim3(256), 0, stream, p);
+    if (!fast32) return MM_DENSE_GENERIC;
+    return p.ne11 >= 64 && p.ne01 >= 8 ? MM_DENSE_F32_ROWS : MM_DENSE_F32_VEC;
+}
+
+// The grid of the wave-per-row kernels is (rows, column tiles of 8, ne12*ne13): dims y and z of a grid end at 65535, so a launch covers at most that
+// many column tiles and batches and the rest goes into further launches that start at (y0, z0). One launch for every shape a model produces.
+constexpr int64_t MM_DENSE_GRID_YZ = 65535;
+template <typename K> static int mm_dense_launch(K kernel, int64_t rows_per_block, const mm_dense_args & p, hipStream_t stream) {      // -> the number of launches
+    constexpr int NC = 8;
+    const int64_t ny = (p.ne11 + NC - 1)/NC, nz = p.ne12*p.ne13;
+    int n = 0;
+    for (int64_t z0 = 0; z0 < nz; z0 += MM_DENSE_GRID_YZ) {
+        for (int64_t y0 = 0; y0 < ny; y0 += MM_DENSE_GRID_YZ) {
+            const dim3 grid((unsigned)((p.ne01 + rows_per_block - 1)/rows_per_block), (unsigned) std::min(ny - y0, MM_DENSE_GRID_YZ), (unsigned) std::min(nz - z0, MM_DENSE_GRID_YZ));
+            hipLaunchKernelGGL(kernel, grid, dim3(256), 0, stream, p, y0, z0);
+            n++;
+        }
     }
-    else if (fast32) hipLaunchKernelGGL((k_mm_dense<NC, 2>), grid, dim3(256), 0, stream, p);
-    else             hipLaunchKernelGGL((k_mm_dense<NC, 0>), grid, dim3(256), 0, stream, p);
+    return n;
+}
+
+mm_dense_path mul_mat_dense(const mm_dense_args & p, void * scratch, size_t scratch_bytes, hipStream_t stream, int * n_launches) {
+    const mm_dense_path path = mul_mat_dense_path(p, scratch_bytes);
+    *n_launches = 0;
+    if (p.ne01 == 0 || p.ne11 == 0 || p.ne12*p.ne13 == 0) return path;
+    constexpr int NC = 8;
+    switch (path) {
+        case MM_DENSE_MFMA:      mul_mat_dense_mfma(p, scratch, stream); *n_launches = 2; break;      // (the f16 copy of b, the product)
+        case MM_DENSE_F16_PAIRS: *n_launches = mm_dense_launch(k_mm_dense<NC, 1>, 4, p, stream); break;
+        case MM_DENSE_F32_ROWS:
+            if (p.ne01 >= 32) *n_launches = mm_dense_launch(k_mm_dense_rows<NC, 4>, 16, p, stream);
+            else              *n_launches = mm_dense_launch(k_mm_dense_rows<NC, 2>, 8, p, stream);      // (few experts: two rows per wave keep enough waves in flight)
+            break;
+        case MM_DENSE_F32_VEC:   *n_launches = mm_dense_launch(k_mm_dense<NC, 2>, 4, p, stream); break;
+        case MM_DENSE_GENERIC:   *n_launches = mm_dense_launch(k_mm_dense<NC, 0>, 4, p, stream); break;
+    }
+    return path;
 }
 
 // ---- MUL_MAT_ID over an F16 / BF16 / F32 expert stack (tests/test-backend-ops.cpp:5821-5824 with base_types F32 / F16; an unquantized MoE checkpoint) ----

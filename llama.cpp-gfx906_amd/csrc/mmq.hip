@@ -1404,7 +1404,7 @@ void mul_mat_q_id(int type_a, const void * W, size_t w_row_stride, size_t w_expe
 // f16 x f32 with ggml broadcast on the matrix cores (n > 8 columns): a rows contiguous f16, b rows contiguous f32
 bool mul_mat_dense_mfma_supported(const mm_dense_args & p) {
     return p.type_a == T_F16 && p.type_b == T_F32 && p.nb00 == 2 && p.nb10 == 4 && p.ne11 > MMVQ_MAX_N && p.ne00 % 32 == 0 &&
-           p.ne12*p.ne13 <= 65535 && p.ne01 < (1ll << 30) && p.ne11 < (1ll << 30);
+           p.ne12*p.ne13 <= 65535 && p.ne01 <= 65535ll*MQ_BM && p.ne11 <= 65535;     // (grid dims y and z end at 65535: k_act_to_16 has a column per grid row, k_mmq a 128-row tile; the batches are dim z of both)
 }
 size_t mul_mat_dense_mfma_scratch_bytes(const mm_dense_args & p) { return mul_mat_q_layout(p.ne10, p.ne11*p.ne12*p.ne13, 0).x_end + 256; }     // the f16 copy of b only
 

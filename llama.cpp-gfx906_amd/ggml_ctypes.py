@@ -68,7 +68,8 @@ class mi355x_counters(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in (
         "graphs_computed", "nodes_computed", "kernels_launched", "graph_replays", "graph_captures", "mmvq_launches",
         "mmq_launches", "weight_bytes", "act_quant_launches", "act_quant_reused", "split_mul_mats",
-        "graph_partial_replays", "moe_combine_direct")]
+        "graph_partial_replays", "moe_combine_direct",
+        "dense_mfma", "dense_f16_pairs", "dense_f32_vec", "dense_f32_rows", "dense_generic", "dense_id")]
 
 
 class mi355x_prof_entry(C.Structure):

@@ -508,7 +508,9 @@ def test_attention_matmuls_f16_kv_views():
         assert orc.nmse(exp_kqv, got_kqv) <= 5e-4
 
 
-def test_mul_mat_f32_f16_generic_strided():
+def test_mul_mat_f32_f16_batched_broadcast():
+    """contiguous F32 / F16 weights x F32, k = 40, n = 9, broadcast 2 in dim 2: the F32 vector kernel and (n > 8, k % 32 != 0) the F16 pair kernel;
+    tests/test_gpu_dense_mul_mat.py holds the layouts, types and kernels this does not reach"""
     rng = np.random.default_rng(12)
     a_ = rng.uniform(-1, 1, size=(2, 3, 16, 40)).astype(np.float32)
     b_ = rng.uniform(-1, 1, size=(2, 6, 9, 40)).astype(np.float32)
