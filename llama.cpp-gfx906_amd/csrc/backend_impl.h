@@ -219,6 +219,20 @@ static inline tensor_desc desc(const struct ggml_tensor * t) {
     for (int i = 0; i < 4; i++) { d.ne[i] = t->ne[i]; d.nb[i] = t->nb[i]; }
     return d;
 }
+// a ROPE node's op_params, and the node as the descriptor a mat-mul launch that applies its rotation carries (no table)
+static inline rope_params rope_params_of(const struct ggml_tensor * rope_node) {
+    rope_params p;
+    p.n_dims = rope_node->op_params[1]; p.mode = rope_node->op_params[2]; p.n_ctx_orig = rope_node->op_params[4];
+    p.freq_base = op_f32(rope_node, 5); p.freq_scale = op_f32(rope_node, 6); p.ext_factor = op_f32(rope_node, 7);
+    p.attn_factor = op_f32(rope_node, 8); p.beta_fast = op_f32(rope_node, 9); p.beta_slow = op_f32(rope_node, 10);
+    return p;
+}
+static inline mmvq_rope mmvq_rope_of(const struct ggml_tensor * rope_node) {
+    mmvq_rope r = {};
+    r.pos = (const int32_t *) rope_node->src[1]->data; r.freq_factors = rope_node->src[2] ? (const float *) rope_node->src[2]->data : nullptr;
+    r.head_dim = (int) rope_node->ne[0]; r.p = rope_params_of(rope_node);
+    return r;
+}
 // the arguments of a dense (F16 / BF16 / F32 src0) MUL_MAT node: what mul_mat_dense_path decides from, for the launch and for the graph's scratch request alike
 static inline mm_dense_args mm_dense_args_of(const struct ggml_tensor * dst) {
     const struct ggml_tensor * a = dst->src[0]; const struct ggml_tensor * b = dst->src[1];

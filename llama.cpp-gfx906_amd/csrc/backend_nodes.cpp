@@ -133,10 +133,12 @@ static void op_mul_mat(mi_backend_ctx * c, struct ggml_tensor * dst, struct ggml
                     const size_t at = c->pass.bf16_at(bp, K, N, b->nb[1]);      // (at any offset: a producer may have left it above its own)
                     const bool ready = at != mi_pass::NO_ACT;
                     const size_t off = ready ? at : 0;
-                    void * scr = (char *) c->scratch + off;
-                    if (out) mul_mat_q((int) a->type, W, a->nb[1], M, K, (const float *) bp, b->nb[1], N, scr, ready, (float *) out->data, out->nb[1],
-                                       (const float *) res->data, res->ne[1] == 1 && N > 1 ? 0 : res->nb[1], c->stream, defer);     // (a bias row: the same addend for every token)
-                    else     mul_mat_q((int) a->type, W, a->nb[1], M, K, (const float *) bp, b->nb[1], N, scr, ready, d, dst->nb[1], nullptr, 0, c->stream);
+                    mmq_call mc = {};
+                    mc.type = (int) a->type; mc.W = W; mc.w_row_stride = a->nb[1]; mc.m = M; mc.stream = c->stream;
+                    mc.act = { (const float *) bp, b->nb[1], K, N, (char *) c->scratch + off, c->scratch_size - off, ready };
+                    mc.dst = out ? (float *) out->data : d; mc.dst_stride = out ? out->nb[1] : dst->nb[1];
+                    if (out) { mc.defer = defer; mc.res = (const float *) res->data; mc.res_stride = res->ne[1] == 1 && N > 1 ? 0 : res->nb[1]; }     // (a bias row: the same addend for every token)
+                    mul_mat_q(mc);
                     if (ready) c->cnt.act_quant_reused++;
                     else c->pass.converted_bf16(bp, K, N, b->nb[1]);
                     if (defer) defer->planes_off += off;      // (mul_mat_q counted from `scr`; now from the start of the scratch)
@@ -201,7 +203,12 @@ static void op_mul_mat_split(mi_backend_ctx * c, struct ggml_tensor * dst) {
             st = pr.stream; scr = pr.scratch;
         }
         if (few) mul_mat_vec_q((int) a->type, e->data[i], a->nb[1], rows, K, q, N, d, dst->nb[1], st);
-        else     mul_mat_q((int) a->type, e->data[i], a->nb[1], rows, K, (const float *) b->data, b->nb[1], N, scr, false, d, dst->nb[1], nullptr, 0, st);
+        else {
+            mmq_call mc = {};
+            mc.type = (int) a->type; mc.W = e->data[i]; mc.w_row_stride = a->nb[1]; mc.m = rows; mc.stream = st; mc.dst = d; mc.dst_stride = dst->nb[1];
+            mc.act = { (const float *) b->data, b->nb[1], K, N, scr, need, false };
+            mul_mat_q(mc);
+        }
         c->cnt.kernels_launched++; c->cnt.weight_bytes += (uint64_t) rows*a->nb[1];
         if (few) c->cnt.mmvq_launches++; else c->cnt.mmq_launches++;
         if (!local) { MI_CHECK_G(hipEventRecord(c->peers[i].done, st)); waited[i] = true; }
@@ -211,6 +218,13 @@ static void op_mul_mat_split(mi_backend_ctx * c, struct ggml_tensor * dst) {
     c->cnt.split_mul_mats++;
 }
 
+// a launch over the expert stack `as` ([k, m, n_expert]) for the pairs of `ids`: what the caller adds is the input, the epilogue and dst
+static mmq_moe_call moe_call_of(mi_backend_ctx * c, const struct ggml_tensor * as, const struct ggml_tensor * ids) {
+    mmq_moe_call mc = {};
+    mc.type = (int) as->type; mc.W = as->data; mc.w_row_stride = as->nb[1]; mc.w_expert_stride = as->nb[2]; mc.m = as->ne[1]; mc.k = as->ne[0]; mc.n_expert = as->ne[2];
+    mc.ids = (const int32_t *) ids->data; mc.ids_nb0 = ids->nb[0]; mc.ids_nb1 = ids->nb[1]; mc.n_used = ids->ne[0]; mc.n_tokens = ids->ne[1]; mc.stream = c->stream;
+    return mc;
+}
 static void op_mul_mat_id(mi_backend_ctx * c, struct ggml_tensor * dst) {
     const struct ggml_tensor * as  = dst->src[0];
     const struct ggml_tensor * b   = dst->src[1];
@@ -228,9 +242,10 @@ static void op_mul_mat_id(mi_backend_ctx * c, struct ggml_tensor * dst) {
     // below would read every expert matrix once per pair
     if (n_used*n_tokens > 4*MMVQ_MAX_N && mul_mat_q_id_supported(as->ne[2], n_used, n_tokens) && dst->nb[0] == sizeof(float)) {
         c->pass.drop_act();   // the scratch is reused
-        mul_mat_q_id((int) as->type, as->data, as->nb[1], as->nb[2], M, K, (const float *) b->data, b->nb[1], b->nb[2], n_b,
-                     (const int32_t *) ids->data, ids->nb[0], ids->nb[1], n_used, n_tokens, as->ne[2],
-                     c->scratch, (float *) dst->data, dst->nb[1], dst->nb[2], c->stream);
+        mmq_moe_call mc = moe_call_of(c, as, ids);
+        mc.n_b = n_b; mc.b = (const float *) b->data; mc.b_nb1 = b->nb[1]; mc.b_nb2 = b->nb[2]; mc.scratch = c->scratch;
+        mc.dst = (float *) dst->data; mc.dst_nb1 = dst->nb[1]; mc.dst_nb2 = dst->nb[2];
+        mul_mat_q_id(mc);
         c->cnt.mmq_launches++; c->cnt.kernels_launched += 3;
         c->cnt.weight_bytes += (uint64_t) as->ne[2]*M*ggml_row_size(as->type, K);
         return;
@@ -340,12 +355,7 @@ static mmv_chain match_mmv_chain(mi_backend_ctx * c, const struct ggml_cgraph * 
             rp->op_params[1] % 2 == 0 && rp->ne[0] % 2 == 0 && a->ne[1] % 2 == 0 && rp->src[1]->type == GGML_TYPE_I32) {
             ch.grp.dst = (float *) rp->data; ch.grp.epi = EPI_ROPE; ch.last = ir + 1; ch.has_rope = true;
             ch.grp.res = bias ? (const float *) bias->data : nullptr;
-            ch.rope.pos = (const int32_t *) rp->src[1]->data;
-            ch.rope.freq_factors = rp->src[2] ? (const float *) rp->src[2]->data : nullptr;
-            ch.rope.head_dim = (int) rp->ne[0];
-            ch.rope.p.n_dims = rp->op_params[1]; ch.rope.p.mode = rp->op_params[2]; ch.rope.p.n_ctx_orig = rp->op_params[4];
-            ch.rope.p.freq_base = op_f32(rp, 5); ch.rope.p.freq_scale = op_f32(rp, 6); ch.rope.p.ext_factor = op_f32(rp, 7);
-            ch.rope.p.attn_factor = op_f32(rp, 8); ch.rope.p.beta_fast = op_f32(rp, 9); ch.rope.p.beta_slow = op_f32(rp, 10);
+            ch.rope = mmvq_rope_of(rp);
             ch.out_ptr = rp->data; ch.out_bytes = ggml_nbytes(rp);
             return ch;
         }
@@ -996,59 +1006,36 @@ static int try_fused_prefill_moe(mi_backend_ctx * c, struct ggml_cgraph * g, int
             }
         }
     }
-    const mmq_moe_plan pl = mul_mat_q_id_plan(c->scratch, K, n_tokens, n_used, E, M);
+    const mmq_moe_plan pl = mul_mat_q_id_plan(c->scratch, K, n_tokens, n_used, E, M, c->moe_dual);
     if (pl.bytes > c->scratch_size) return 0;
     const bool gl_f32 = !down || !is_internal(c, gl);      // somebody else reads the GLU result as a tensor
     c->pass.drop_act();     // the scratch is reused
-    // Few pairs per expert (gpt-oss at 512 tokens: 64): the dual kernel — one 256-pair tile per expert, eight decoding waves, both tensors against one activation tile
-    // (pp512 18.7k -> 22.2k tok/s). Many (Mixtral: ~128): the dual kernel's single workgroup per CU decodes at half the rate of two 128-pair workgroups (926 us against
-    // 2 x 350 - 390 + 62 for the GLU kernel), so the two products stay separate launches of the 128-pair kernel: the up launch writes its tensor, the gate launch reads
-    // it back in its epilogue and evaluates the GLU there.
-    static const int dual_env = (int) env_int("GGML_MI355X_MOE_DUAL", -1);
-    const int dual_opt = c->moe_dual >= 0 ? c->moe_dual : dual_env;
-    const bool dual = dual_opt >= 0 ? dual_opt != 0 : n_used*n_tokens <= 96*E;
-    const int tile = dual ? 256 : mul_mat_q_id_tile(n_used, n_tokens, E);
-    if (!dual && gl_f32) {      // the gate launch reads the up tensor while it writes the GLU tensor: the same element by the same lane if they are one buffer, a race if they overlap otherwise
-        const struct ggml_tensor * u_chk = a_is_gate ? o_out : a_out;
-        if (gl->data != u_chk->data && ranges_overlap(gl->data, ggml_nbytes(gl), u_chk->data, ggml_nbytes(u_chk))) return 0;
-    }
-    mul_mat_q_id_act16((const float *) b->data, b->nb[1], b->nb[2], K, 1, n_tokens, pl.xb, c->stream);
-    mul_mat_q_id_sort((const int32_t *) ids->data, ids->nb[0], ids->nb[1], n_used, n_tokens, E, tile, pl.table, c->stream);
-    mmq_moe_epi eg;
-    eg.oai = oai ? 1 : 0; eg.alpha = oai ? op_f32(gl, 2) : 0.0f; eg.limit = oai ? op_f32(gl, 3) : 0.0f;
-    if (dual) {
-        if (bg) { eg.bias = (const float *) bg->src[1]->data; eg.bias2 = (const float *) bu->src[1]->data; eg.bias_stride = bg->src[1]->nb[1]/4; }
-        mul_mat_q_id_tiles((int) as->type, w_gate->data, w_up->data, as->nb[1], as->nb[2], M, K, pl.xb, 1, pl.table, tile, n_used, n_tokens, E, eg,
-                           gl_f32 ? (float *) gl->data : nullptr, gl->nb[1], gl->nb[2], down ? pl.y16 : nullptr, c->stream);
-        c->cnt.mmq_launches++; c->cnt.kernels_launched += 3;
-    } else {
-        struct ggml_tensor * u_out = a_is_gate ? o_out : a_out;       // the up side's last tensor: its memory holds the up product (+ bias) between the two launches
-        mmq_moe_epi eu;
-        if (bu) { eu.bias = (const float *) bu->src[1]->data; eu.bias_stride = bu->src[1]->nb[1]/4; }
-        mul_mat_q_id_tiles((int) as->type, w_up->data, nullptr, as->nb[1], as->nb[2], M, K, pl.xb, 1, pl.table, tile, n_used, n_tokens, E, eu,
-                           (float *) u_out->data, u_out->nb[1], u_out->nb[2], nullptr, c->stream);
-        if (bg) { eg.bias = (const float *) bg->src[1]->data; eg.bias_stride = bg->src[1]->nb[1]/4; }
-        eg.glu_up = (const float *) u_out->data; eg.glu_up_nb1 = u_out->nb[1]; eg.glu_up_nb2 = u_out->nb[2];
-        mul_mat_q_id_tiles((int) as->type, w_gate->data, nullptr, as->nb[1], as->nb[2], M, K, pl.xb, 1, pl.table, tile, n_used, n_tokens, E, eg,
-                           gl_f32 ? (float *) gl->data : nullptr, gl->nb[1], gl->nb[2], down ? pl.y16 : nullptr, c->stream);
-        c->cnt.mmq_launches += 2; c->cnt.kernels_launched += 4;
-    }
+    // the up side's last tensor: in the two-launch form its memory holds the up product (+ bias) between the two launches, and the gate launch reads it while it writes the
+    // GLU tensor: the same element by the same lane if they are one buffer, a race if they overlap otherwise
+    struct ggml_tensor * u_out = a_is_gate ? o_out : a_out;
+    if (!pl.dual && gl_f32 && gl->data != u_out->data && ranges_overlap(gl->data, ggml_nbytes(gl), u_out->data, ggml_nbytes(u_out))) return 0;
+    mmq_moe_call gu = moe_call_of(c, w_gate, ids);
+    gu.W2 = w_up->data; gu.b = (const float *) b->data; gu.b_nb1 = b->nb[1]; gu.b_nb2 = b->nb[2];
+    gu.epi.oai = oai ? 1 : 0; gu.epi.alpha = oai ? op_f32(gl, 2) : 0.0f; gu.epi.limit = oai ? op_f32(gl, 3) : 0.0f;
+    if (bg) { gu.epi.bias = (const float *) bg->src[1]->data; gu.epi.bias2 = (const float *) bu->src[1]->data; gu.epi.bias_stride = bg->src[1]->nb[1]/4; }
+    if (!pl.dual) { gu.epi.glu_up = (const float *) u_out->data; gu.epi.glu_up_nb1 = u_out->nb[1]; gu.epi.glu_up_nb2 = u_out->nb[2]; }
+    gu.dst = gl_f32 ? (float *) gl->data : nullptr; gu.dst_nb1 = gl->nb[1]; gu.dst_nb2 = gl->nb[2]; gu.y16 = down ? pl.y16 : nullptr;
+    mul_mat_q_id_gate_up(gu, pl);
+    c->cnt.mmq_launches += pl.dual ? 1 : 2; c->cnt.kernels_launched += pl.dual ? 3 : 4;      // copy, sort, the dual launch | the up and the gate launch
     c->cnt.weight_bytes += (uint64_t) 2*E*M*ggml_row_size(as->type, K);
     if (down) {
-        if (between_to > between_from) {
+        if (between_to > between_from) {      // (not earlier: an allocator may have given these nodes the up tensor's memory, dead in graph order, which the gate launch reads)
             const bool uf = c->use_fusion; c->use_fusion = false;
             for (int q = between_from; q < between_to; ) q += compute_node(c, g, q);
             c->use_fusion = uf;
         }
         const struct ggml_tensor * ad = down->src[0];
-        mmq_moe_epi ed;
-        if (d_bias) { ed.bias = (const float *) d_bias->data; ed.bias_stride = d_bias->nb[1]/4; }
-        if (d_scale) { ed.scale = (const float *) d_scale->data; ed.scale_nb0 = d_scale->nb[1]; ed.scale_nb1 = d_scale->nb[2]; }
-        const int tile_d = mul_mat_q_id_tile(n_used, n_tokens, E);
-        if (tile_d != tile) mul_mat_q_id_sort((const int32_t *) ids->data, ids->nb[0], ids->nb[1], n_used, n_tokens, E, tile_d, pl.table2, c->stream);
-        mul_mat_q_id_tiles((int) ad->type, ad->data, nullptr, ad->nb[1], ad->nb[2], ad->ne[1], M, pl.y16, n_used, tile_d != tile ? pl.table2 : pl.table, tile_d, n_used, n_tokens, E, ed,
-                           (float *) d_out->data, d_out->nb[1], d_out->nb[2], nullptr, c->stream);
-        c->cnt.mmq_launches++; c->cnt.kernels_launched += tile_d != tile ? 2 : 1;
+        mmq_moe_call dc = moe_call_of(c, ad, ids);
+        if (d_bias) { dc.epi.bias = (const float *) d_bias->data; dc.epi.bias_stride = d_bias->nb[1]/4; }
+        if (d_scale) { dc.epi.scale = (const float *) d_scale->data; dc.epi.scale_nb0 = d_scale->nb[1]; dc.epi.scale_nb1 = d_scale->nb[2]; }
+        dc.dst = (float *) d_out->data; dc.dst_nb1 = d_out->nb[1]; dc.dst_nb2 = d_out->nb[2];
+        mul_mat_q_id_down(dc, pl);
+        c->cnt.mmq_launches++; c->cnt.kernels_launched += pl.tile_down != pl.tile ? 2 : 1;      // (a second sort when the down launch's tiles differ)
         c->cnt.weight_bytes += (uint64_t) E*ad->ne[1]*ggml_row_size(ad->type, M);
     }
     return consumed_to - i + 1;
@@ -1124,8 +1111,11 @@ static int try_fused_prefill_glu(mi_backend_ctx * c, struct ggml_cgraph * g, int
     const size_t off2 = mul_mat_q_x_bytes(K, N);
     const bool y16 = down && off2 + mul_mat_q_scratch_bytes(M, N, down->src[0]->ne[1]) <= c->scratch_size;
     prof_begin(c, (int) a->type, 2*M, K, N, (uint64_t) 2*M*ggml_row_size(a->type, K));
-    mul_mat_q_glu((int) a->type, gl->src[0]->src[0]->data, gl->src[1]->src[0]->data, a->nb[1], M, K, (const float *) b->data, b->nb[1], N,
-                  c->scratch, ready, y16 ? nullptr : (float *) gl->data, gl->nb[1], c->stream, y16 ? (uint16_t *) ((char *) c->scratch + off2) : nullptr);
+    mmq_call mc = {};
+    mc.type = (int) a->type; mc.W = gl->src[0]->src[0]->data; mc.W2 = gl->src[1]->src[0]->data; mc.w_row_stride = a->nb[1]; mc.m = M; mc.stream = c->stream;
+    mc.act = { (const float *) b->data, b->nb[1], K, N, c->scratch, c->scratch_size, ready };
+    mc.dst = y16 ? nullptr : (float *) gl->data; mc.dst_stride = gl->nb[1]; mc.y16 = y16 ? (uint16_t *) ((char *) c->scratch + off2) : nullptr;
+    mul_mat_q_glu(mc);
     prof_end(c);
     if (ready) c->cnt.act_quant_reused++;
     if (y16) c->pass.produced_bf16(i, j2, gl->data, M, N, gl->nb[1], off2);
@@ -1177,38 +1167,34 @@ static int try_fused_prefill_qkv(mi_backend_ctx * c, struct ggml_cgraph * g, int
             }
         }
     }
-    int types[3]; const void * W[3]; size_t wrs[3]; int64_t m[3]; float * dst[3]; size_t dstride[3];
-    uint64_t wbytes = 0;
+    const int64_t K = b->ne[0], N = b->ne[1];
+    const bool ready = c->pass.bf16_at(b->data, K, N, b->nb[1]) == 0;      // (at the start only: this launch reads its activations there)
+    mmq_multi_call plain = {};      // the plain grouped launch: every mat-mul writes its own tensor, the ADDs and ROPEs run behind it
+    plain.nseg = nc; plain.stream = c->stream; plain.act = { (const float *) b->data, b->nb[1], K, N, c->scratch, c->scratch_size, ready };
+    uint64_t wbytes = 0; int64_t m_tot = 0;
+    for (int q = 0; q < nc; q++) {
+        const struct ggml_tensor * n = g->nodes[ch[q].mm]; const struct ggml_tensor * a = n->src[0]; mmq_multi_seg & sg = plain.seg[q];
+        sg.type = (int) a->type; sg.W = a->data; sg.w_row_stride = a->nb[1]; sg.m = a->ne[1]; sg.dst = (float *) n->data; sg.dst_stride = n->nb[1];
+        wbytes += (uint64_t) a->ne[1]*ggml_row_size(a->type, a->ne[0]); m_tot += a->ne[1];
+    }
     // the ROPEs go into the launch (epilogue, or the pass that combines split-k planes) when they are NORM-mode, share one descriptor and
     // are the only readers of their mat-muls: the mat-mul then writes the ROPE node's tensor directly
-    mmvq_rope rd = {}; bool have_rd = false, rope_ok = !any_add; int seg_rope[3] = { 0, 0, 0 };
+    mmq_multi_call roped = plain; bool have_rd = false, rope_ok = !any_add;
     for (int q = 0; q < nc && rope_ok; q++) {
         if (ch[q].rope < 0) continue;
         const struct ggml_tensor * mm = g->nodes[ch[q].mm]; const struct ggml_tensor * rp = g->nodes[ch[q].rope];
-        mmvq_rope r1 = {};
-        r1.pos = (const int32_t *) rp->src[1]->data; r1.freq_factors = rp->src[2] ? (const float *) rp->src[2]->data : nullptr; r1.head_dim = (int) rp->ne[0];
-        r1.p.n_dims = rp->op_params[1]; r1.p.mode = rp->op_params[2]; r1.p.n_ctx_orig = rp->op_params[4];
-        r1.p.freq_base = op_f32(rp, 5); r1.p.freq_scale = op_f32(rp, 6); r1.p.ext_factor = op_f32(rp, 7);
-        r1.p.attn_factor = op_f32(rp, 8); r1.p.beta_fast = op_f32(rp, 9); r1.p.beta_slow = op_f32(rp, 10);
+        const mmvq_rope r1 = mmvq_rope_of(rp);
         rope_ok = rp->op_params[2] == 0 && rp->type == GGML_TYPE_F32 && ggml_is_contiguous(rp) && rp->src[1]->type == GGML_TYPE_I32 && rp->ne[3] == 1 &&
                   rp->ne[2] == b->ne[1] && rp->ne[0]*rp->ne[1] == mm->ne[0] && rp->op_params[1] % 2 == 0 && rp->op_params[1] <= rp->ne[0] && rp->ne[0] % 4 == 0 &&
                   ggml_nelements(rp->src[1]) == b->ne[1] && is_internal(c, mm) && (rp->src[0] == mm || is_internal(c, rp->src[0])) &&
-                  (!have_rd || memcmp(&rd, &r1, sizeof(rd)) == 0);
-        rd = r1; have_rd = true; seg_rope[q] = 1;
+                  (!have_rd || memcmp(&roped.rope, &r1, sizeof(r1)) == 0);
+        roped.rope = r1; have_rd = true; roped.seg[q].rope = true; roped.seg[q].dst = (float *) rp->data; roped.seg[q].dst_stride = rp->nb[2];
     }
     const bool fuse_rope = have_rd && rope_ok;
-    for (int q = 0; q < nc; q++) {
-        const struct ggml_tensor * n = g->nodes[ch[q].mm]; const struct ggml_tensor * a = n->src[0];
-        types[q] = (int) a->type; W[q] = a->data; wrs[q] = a->nb[1]; m[q] = a->ne[1]; dst[q] = (float *) n->data; dstride[q] = n->nb[1];
-        if (fuse_rope && seg_rope[q]) { dst[q] = (float *) g->nodes[ch[q].rope]->data; dstride[q] = g->nodes[ch[q].rope]->nb[2]; }
-        wbytes += (uint64_t) a->ne[1]*ggml_row_size(a->type, a->ne[0]);
-    }
-    const int64_t K = b->ne[0], N = b->ne[1];
-    const bool ready = c->pass.bf16_at(b->data, K, N, b->nb[1]) == 0;      // (at the start only: this launch reads its activations there)
-    prof_begin(c, types[0], m[0] + m[1] + (nc > 2 ? m[2] : 0), K, N, wbytes);
+    prof_begin(c, plain.seg[0].type, m_tot, K, N, wbytes);
     // the KV-cache writes that follow (SET_ROWS of rope(k) as f16 rows, SET_ROWS of v as an element scatter into the transposed cache — the pair
     // try_fused_kv_store takes) ride on the same combine pass
-    mmq_kv_store kvs = {}; bool have_kvs = false; int kv_last = -1;
+    int kv_last = -1;
     if (fuse_rope) {
         const int j1 = next_real(g, ch[nc - 1].end), j2 = j1 > 0 ? next_real(g, j1) : -1;
         if (j2 > 0 && g->nodes[j1]->op == GGML_OP_SET_ROWS && g->nodes[j2]->op == GGML_OP_SET_ROWS) {
@@ -1216,58 +1202,47 @@ static int try_fused_prefill_qkv(mi_backend_ctx * c, struct ggml_cgraph * g, int
             const struct ggml_tensor * ks = sk->src[0]; const struct ggml_tensor * ki = sk->src[1];
             const struct ggml_tensor * vs = sv->src[0]; const struct ggml_tensor * vi = sv->src[1];
             int qk = -1, qv = -1;
-            for (int q = 0; q < nc; q++) { if (ks->data == (void *) dst[q]) qk = q; if (vs->data == (void *) dst[q]) qv = q; }
+            for (int q = 0; q < nc; q++) { if (ks->data == (void *) roped.seg[q].dst) qk = q; if (vs->data == (void *) roped.seg[q].dst) qv = q; }
+            const int64_t mk = qk >= 0 ? roped.seg[qk].m : 0, mv = qv >= 0 ? roped.seg[qv].m : 0;
             const bool ok = qk >= 0 && qv >= 0 && qk != qv && sk->type == GGML_TYPE_F16 && sv->type == GGML_TYPE_F16 && ks->type == GGML_TYPE_F32 && vs->type == GGML_TYPE_F32 &&
                 ki->type == GGML_TYPE_I64 && vi->type == GGML_TYPE_I64 && ggml_is_contiguous(ki) && ggml_is_contiguous(vi) &&
-                ks->ne[0] == m[qk] && ks->ne[1] == N && ks->ne[2] == 1 && ks->ne[3] == 1 && ks->nb[0] == 4 && ks->nb[1] == (size_t) m[qk]*4 && dstride[qk] == (size_t) m[qk]*4 &&
-                sk->nb[0] == 2 && sk->nb[1] % 8 == 0 && ((uintptr_t) sk->data % 8) == 0 && ggml_nelements(ki) == N && m[qk] % 4 == 0 &&
-                vs->ne[0] == 1 && vs->ne[1] == m[qv]*N && vs->ne[2] == 1 && vs->ne[3] == 1 && vs->nb[1] == 4 && dstride[qv] == (size_t) m[qv]*4 &&
-                sv->ne[0] == 1 && sv->nb[1] == 2 && ggml_nelements(vi) == m[qv]*N &&
+                ks->ne[0] == mk && ks->ne[1] == N && ks->ne[2] == 1 && ks->ne[3] == 1 && ks->nb[0] == 4 && ks->nb[1] == (size_t) mk*4 && roped.seg[qk].dst_stride == (size_t) mk*4 &&
+                sk->nb[0] == 2 && sk->nb[1] % 8 == 0 && ((uintptr_t) sk->data % 8) == 0 && ggml_nelements(ki) == N && mk % 4 == 0 &&
+                vs->ne[0] == 1 && vs->ne[1] == mv*N && vs->ne[2] == 1 && vs->ne[3] == 1 && vs->nb[1] == 4 && roped.seg[qv].dst_stride == (size_t) mv*4 &&
+                sv->ne[0] == 1 && sv->nb[1] == 2 && ggml_nelements(vi) == mv*N &&
                 !ranges_overlap(sk->data, ggml_nbytes(sk), b->data, ggml_nbytes(b)) && !ranges_overlap(sv->data, ggml_nbytes(sv), b->data, ggml_nbytes(b));
             if (ok) {
-                kvs.st16[qk] = (uint16_t *) sk->data; kvs.st_idx[qk] = (const int64_t *) ki->data; kvs.st_row_elems[qk] = (int64_t)(sk->nb[1]/2); kvs.st_mode[qk] = 1;
-                kvs.st16[qv] = (uint16_t *) sv->data; kvs.st_idx[qv] = (const int64_t *) vi->data; kvs.st_row_elems[qv] = 0; kvs.st_mode[qv] = 2;
-                have_kvs = true; kv_last = j2;
+                mmq_multi_seg & gk = roped.seg[qk]; mmq_multi_seg & gv = roped.seg[qv];
+                gk.st16 = (uint16_t *) sk->data; gk.st_idx = (const int64_t *) ki->data; gk.st_row_elems = (int64_t)(sk->nb[1]/2); gk.st_mode = 1;
+                gv.st16 = (uint16_t *) sv->data; gv.st_idx = (const int64_t *) vi->data; gv.st_row_elems = 0; gv.st_mode = 2;
+                kv_last = j2;
             }
         }
     }
     // bias rows (ADD behind a mat-mul, the mat-mul read by nobody else): the launch's epilogue adds them and writes the ADD's tensor
-    const float * seg_bias[3] = { nullptr, nullptr, nullptr }; float * bdst[3]; size_t bdstride[3]; bool biased = any_add;
-    for (int q = 0; q < nc && biased; q++) {
-        bdst[q] = dst[q]; bdstride[q] = dstride[q];
+    mmq_multi_call biased = plain; bool bias_ok = any_add;
+    for (int q = 0; q < nc && bias_ok; q++) {
         if (ch[q].add < 0) continue;
         const struct ggml_tensor * mm = g->nodes[ch[q].mm]; const struct ggml_tensor * ad = g->nodes[ch[q].add];
         const struct ggml_tensor * bt = ad->src[0] == mm ? ad->src[1] : ad->src[0];
-        biased = is_internal(c, mm) && ad->type == GGML_TYPE_F32 && ggml_are_same_shape(ad, mm) && ad->nb[0] == 4 && bt->type == GGML_TYPE_F32 && bt->ne[0] == m[q] &&
-                 ggml_nelements(bt) == m[q] && bt->nb[0] == 4;
-        seg_bias[q] = (const float *) bt->data; bdst[q] = (float *) ad->data; bdstride[q] = ad->nb[1];
+        bias_ok = is_internal(c, mm) && ad->type == GGML_TYPE_F32 && ggml_are_same_shape(ad, mm) && ad->nb[0] == 4 && bt->type == GGML_TYPE_F32 && bt->ne[0] == mm->ne[0] &&
+                  ggml_nelements(bt) == mm->ne[0] && bt->nb[0] == 4;
+        biased.seg[q].bias = (const float *) bt->data; biased.seg[q].dst = (float *) ad->data; biased.seg[q].dst_stride = ad->nb[1];
     }
-    bool roped = fuse_rope, stored = have_kvs;
-    if (biased && mul_mat_q_multi(nc, types, W, wrs, m, bdst, bdstride, K, (const float *) b->data, b->nb[1], N, c->scratch, c->scratch_size, ready, nullptr, nullptr, nullptr, c->stream, seg_bias)) {
-        prof_end(c);
-        if (ready) c->cnt.act_quant_reused++;
-        else c->pass.converted_bf16(b->data, K, N, b->nb[1]);
-        c->cnt.mmq_launches++; c->cnt.kernels_launched += ready ? 1 : 2; c->cnt.weight_bytes += wbytes;
-        for (int q = 0; q < nc; q++) if (ch[q].rope >= 0) compute_node(c, g, ch[q].rope);
-        return ch[nc - 1].end - i + 1;
-    }
-    bool done = fuse_rope && mul_mat_q_multi(nc, types, W, wrs, m, dst, dstride, K, (const float *) b->data, b->nb[1], N, c->scratch, c->scratch_size, ready, &rd, seg_rope,
-                                             have_kvs ? &kvs : nullptr, c->stream);
-    if (!done) {
-        roped = false; stored = false;
-        for (int q = 0; q < nc; q++) { dst[q] = (float *) g->nodes[ch[q].mm]->data; dstride[q] = g->nodes[ch[q].mm]->nb[1]; }
-        done = mul_mat_q_multi(nc, types, W, wrs, m, dst, dstride, K, (const float *) b->data, b->nb[1], N, c->scratch, c->scratch_size, ready, nullptr, nullptr, nullptr, c->stream);
-    }
+    // what the launcher takes: with the bias rows (no k split), else with the rotations and cache writes (a k split), else plain; none: the mat-muls run one by one
+    const mmq_multi_call * take = bias_ok && mul_mat_q_multi_takes(biased) ? &biased : fuse_rope && mul_mat_q_multi_takes(roped) ? &roped :
+                                  mul_mat_q_multi_takes(plain) ? &plain : nullptr;
+    if (take) mul_mat_q_multi(*take);
     prof_end(c);
-    if (!done) { if (c->profiling && !c->prof_suspend) c->prof.pop_back(); return 0; }
+    if (!take) { if (c->profiling && !c->prof_suspend) c->prof.pop_back(); return 0; }
     if (ready) c->cnt.act_quant_reused++;
     else c->pass.converted_bf16(b->data, K, N, b->nb[1]);
     c->cnt.mmq_launches++; c->cnt.kernels_launched += ready ? 1 : 2; c->cnt.weight_bytes += wbytes;
-    for (int q = 0; q < nc; q++) {
-        if (ch[q].add >= 0) compute_node(c, g, ch[q].add);
-        if (!roped && ch[q].rope >= 0) compute_node(c, g, ch[q].rope);
+    for (int q = 0; q < nc; q++) {      // what did not ride
+        if (take != &biased && ch[q].add >= 0) compute_node(c, g, ch[q].add);
+        if (take != &roped && ch[q].rope >= 0) compute_node(c, g, ch[q].rope);
     }
-    return (stored ? kv_last : ch[nc - 1].end) - i + 1;
+    return (take == &roped && kv_last >= 0 ? kv_last : ch[nc - 1].end) - i + 1;
 }
 
 // Prefill: MUL_MAT -> ADD(residual) (build_attn's wo, build_ffn's down: src/llama-model.cpp:6057,6096) — the residual is added in the
@@ -1429,14 +1404,10 @@ int compute_node(mi_backend_ctx * c, struct ggml_cgraph * g, int i) {
                 glu((int) ggml_get_glu_op(node), node->op_params[1] != 0, desc(s0), s1 ? &b : nullptr, desc(node), op_f32(node, 2), op_f32(node, 3), c->stream);
                 c->cnt.kernels_launched++;
             } break;
-            case GGML_OP_ROPE: {
-                rope_params p;
-                p.n_dims = node->op_params[1]; p.mode = node->op_params[2]; p.n_ctx_orig = node->op_params[4];
-                p.freq_base = op_f32(node, 5); p.freq_scale = op_f32(node, 6); p.ext_factor = op_f32(node, 7);
-                p.attn_factor = op_f32(node, 8); p.beta_fast = op_f32(node, 9); p.beta_slow = op_f32(node, 10);
-                rope(desc(s0), (const int32_t *) s1->data, node->src[2] ? (const float *) node->src[2]->data : nullptr, desc(node), p, c->stream);
+            case GGML_OP_ROPE:
+                rope(desc(s0), (const int32_t *) s1->data, node->src[2] ? (const float *) node->src[2]->data : nullptr, desc(node), rope_params_of(node), c->stream);
                 c->cnt.kernels_launched++;
-            } break;
+                break;
             case GGML_OP_SOFT_MAX: {
                 tensor_desc m;
                 if (s1) m = desc(s1);

@@ -67,66 +67,76 @@ void mul_mat_vec_q_id(int type_a, const void * W, size_t w_row_stride, size_t w_
                       int64_t n_used, int64_t n_tokens, int64_t n_b,
                       float * dst, size_t dst_nb1, size_t dst_nb2, hipStream_t stream);
 
+// ---- the rotary embedding's descriptors: ROPE's op_params, and what a mat-mul launch that applies the rotation carries (the grouped mat-vec's EPI_ROPE, the grouped prefill launch) ----
+struct rope_params {
+    int n_dims, mode, n_ctx_orig;
+    float freq_base, freq_scale, ext_factor, attn_factor, beta_fast, beta_slow;
+};
+// table (the grouped mat-vec only): n_dims/2 x (cos, sin) for the token at pos[0], filled by mul_mat_vec_q_fused_rope_table on the same stream before the launch
+// (one tiny launch per token and rope configuration instead of powf / cosf / sinf per row pair inside every norm+QKV launch)
+struct mmvq_rope { const int32_t * pos; const float * freq_factors; int head_dim; rope_params p; const float * table; };
 // ---- quantized mat-mat (prefill, n > MMVQ_MAX_N): dequantize-to-bf16 tiles in LDS + v_mfma_f32_32x32x16_bf16 ----
-// Host side (mmq.hip): every launch form asks a pure plan function (mmq_plan_one / _multi / _glu: tile size, k split, grid, 16-wave kernel or not) and
-// mul_mat_q_layout for where things sit in the scratch, then only sets pointers and launches.
-// x: f32 rows of k floats at x + i*x_row_stride; scratch: mul_mat_q_scratch_bytes(k, n, m) bytes (the bf16 copy of x + the split-K planes)
-// (scratch_ready: it already holds the copy of exactly this x — the caller's cache — so the conversion pass is skipped)
-// res != NULL: dst = W.x + res (f32 rows of m floats at res + i*res_row_stride; may be dst itself) — the residual ADD of build_attn / build_ffn
-// the scratch of one launch: the bf16 copy of x in [0, x_end), n_planes split-k planes (dense [n][m] f32 each) from planes_off; total includes the slack
+// Every launcher takes ONE named record (value-initialise, fill by name, as attn_call), asks a pure plan function (mmq.hip: mmq_plan_one / _multi / _glu: tile size, k split, grid,
+// 16-wave kernel or not) and mul_mat_q_layout for where things sit in the scratch, then only sets pointers and launches. The scratch of one launch: the bf16 copy of x in [0, x_end), n_planes split-k planes (dense [n][m] f32 each) from planes_off; total includes the slack
 // behind them. A producer kernel that writes the next mat-mul's copy while this one's is still read puts it at x_end as well.
 struct mmq_layout { size_t x_end, planes_off, planes_bytes, total; };
 mmq_layout mul_mat_q_layout(int64_t k, int64_t n, int64_t m, int n_planes = 4);
 size_t mul_mat_q_scratch_bytes(int64_t k, int64_t n, int64_t m);     // = layout(k, n, m).total
-void mul_mat_q(int type_a, const void * W, size_t w_row_stride, int64_t m, int64_t k,
-               const float * x, size_t x_row_stride, int64_t n, void * scratch, bool scratch_ready, float * dst, size_t dst_col_stride_bytes,
-               const float * res, size_t res_row_stride, hipStream_t stream, struct mmq_deferred * defer = nullptr);
+size_t mul_mat_q_x_bytes(int64_t k, int64_t n);      // size of the bf16 activation copy at the start of the scratch (= layout(k, n, 0).x_end)
+// the activations of a prefill launch, shared by the three forms below. x: f32 rows of k floats at x + i*x_row_stride, n of them; scratch: scratch_size bytes, at least mul_mat_q_scratch_bytes(k, n, m)
+// (only the grouped launch's question reads the size); scratch_ready: it already holds the copy of exactly this x — the caller's cache — so the conversion pass is skipped
+struct mmq_act { const float * x; size_t x_row_stride; int64_t k, n; void * scratch; size_t scratch_size; bool scratch_ready; };
 // defer != NULL: when the launch splits k, the pass that adds the planes (and res) is left to the caller (who fuses it with the norm that
 // follows): np = number of planes (0: nothing deferred, dst is complete), planes = dense [np][n][m] f32 in the scratch, planes_off bytes behind `scratch`
 struct mmq_deferred { int np; const float * planes; size_t planes_off; };
-
-struct mmvq_rope;
-// KV-cache writes done by the pass that combines the launch's split-k planes: per segment, mode 0 none | 1 f16 rows st16[idx[token]*st_row_elems + col] |
-// 2 element scatter st16[idx[token*m + col]] (the transposed V cache)
-struct mmq_kv_store { uint16_t * st16[3]; const int64_t * st_idx[3]; int64_t st_row_elems[3]; int st_mode[3]; };
-// 2 or 3 mat-muls on the same activations (wq / wk / wv) as one launch of 256-token tiles; false = not done, run them one by one
-bool mul_mat_q_multi(int nseg, const int * types, const void * const * W, const size_t * w_row_stride, const int64_t * m, float * const * dst, const size_t * dst_stride,
-                     int64_t k, const float * x, size_t x_row_stride, int64_t n, void * scratch, size_t scratch_size, bool scratch_ready,
-                     const struct mmvq_rope * rope, const int * seg_rope, const struct mmq_kv_store * kvs, hipStream_t stream,      // rope != NULL: NORM rotary embedding on the segments flagged in seg_rope
-                     const float * const * seg_bias = nullptr);     // seg_bias[s] != NULL: m[s] floats added to every row of segment s (only without a k split: else false)
-
-// gate / up + SwiGLU for many tokens in one kernel: dst[n][m] = silu(Wg.x) * (Wu.x) (both weight tensors of one type and shape);
-// supported when the 256-token tiles fill the chip
-bool mul_mat_q_glu_supported(int64_t m, int64_t n);
+// mul_mat_q: dst[i*dst_stride + row] = W[row,:] . x[i,:], strides in bytes; res != NULL: dst = W.x + res (f32 rows of m floats at res + i*res_stride; may be dst itself) — the residual
+// ADD of build_attn / build_ffn. mul_mat_q_glu (no res, no defer): gate / up + SwiGLU in one kernel, dst[n][m] = silu(W.x) * (W2.x), both weight tensors of one type and shape;
 // y16 != NULL (m % 64 == 0): the result also (dst == NULL: only) as the bf16 activation copy of the mat-mul that follows (ffn_down), rows of m elements
-void mul_mat_q_glu(int type_a, const void * Wg, const void * Wu, size_t w_row_stride, int64_t m, int64_t k,
-                   const float * x, size_t x_row_stride, int64_t n, void * scratch, bool scratch_ready, float * dst, size_t dst_col_stride_bytes, hipStream_t stream,
-                   uint16_t * y16 = nullptr);
-size_t mul_mat_q_x_bytes(int64_t k, int64_t n);      // size of the bf16 activation copy at the start of the scratch (= layout(k, n, 0).x_end)
+struct mmq_call { int type; const void * W; size_t w_row_stride; int64_t m; mmq_act act; float * dst; size_t dst_stride; const float * res; size_t res_stride;
+                  mmq_deferred * defer; hipStream_t stream; const void * W2; uint16_t * y16; };      // W2, y16: the GLU form only
+void mul_mat_q(const mmq_call & c);
+bool mul_mat_q_glu_supported(int64_t m, int64_t n);      // the 256-token tiles fill the chip
+void mul_mat_q_glu(const mmq_call & c);
+
+// 2 or 3 mat-muls on the same activations (wq / wk / wv) as one launch of 256-token tiles. Per segment: bias != NULL: m floats added to every row (only without a k
+// split); rope: the NORM rotary embedding `rope` on the segment's rows of heads; st_*: the KV-cache write done by the pass that combines the launch's split-k planes:
+// st_mode 0 none | 1 f16 rows st16[st_idx[token]*st_row_elems + col] | 2 element scatter st16[st_idx[token*m + col]] (the transposed V cache)
+struct mmq_multi_seg { int type; const void * W; size_t w_row_stride; int64_t m; float * dst; size_t dst_stride; const float * bias; bool rope;
+                       uint16_t * st16; const int64_t * st_idx; int64_t st_row_elems; int st_mode; };
+struct mmq_multi_call { int nseg; mmq_multi_seg seg[3]; mmq_act act; mmvq_rope rope; hipStream_t stream; };
+// does the grouped launch take this call? Pure: from shapes, types, flags, pointer alignment and the scratch size; no pointer's target is read, nothing is launched. false: too few
+// tiles, an unsupported mix of types or rope shape, a rider that the k split (or its absence) rules out, scratch too small. mul_mat_q_multi only launches: a call it does not take aborts.
+bool mul_mat_q_multi_takes(const mmq_multi_call & c);
+void mul_mat_q_multi(const mmq_multi_call & c);
 
 // ---- MUL_MAT_ID for many tokens (src/llama-graph.cpp:569-595): (token, slot) pairs sorted by expert on the device, then the tiled
 // MFMA kernel per (expert, 128 pairs). b: f32 [k, n_b, n_tokens] (n_b = 1 or n_used); ids: i32 [n_used, n_tokens] (strided);
 // dst: f32 [m, n_used, n_tokens]. No host round trip, so the launch sequence can be captured in a hipGraph.
 bool   mul_mat_q_id_supported(int64_t n_expert, int64_t n_used, int64_t n_tokens);
 size_t mul_mat_q_id_scratch_bytes(int64_t k, int64_t n_b, int64_t n_tokens, int64_t n_used, int64_t n_expert);
-void   mul_mat_q_id(int type_a, const void * W, size_t w_row_stride, size_t w_expert_stride, int64_t m, int64_t k,
-                    const float * b, size_t b_nb1, size_t b_nb2, int64_t n_b,
-                    const int32_t * ids, size_t ids_nb0, size_t ids_nb1, int64_t n_used, int64_t n_tokens, int64_t n_expert,
-                    void * scratch, float * dst, size_t dst_nb1, size_t dst_nb2, hipStream_t stream);
-// The pieces of the above, for the fused expert chain of a prompt pass (backend_nodes.cpp try_fused_prefill_moe): one sort and one bf16 copy of the layer input serve
-// gate, up and down; gate / up run as ONE dual launch with the ADD_ID biases and the (oai) SwiGLU in its epilogue and hand the down projection bf16 rows per pair;
-// the down launch adds its ADD_ID bias and multiplies with the routing weight (MUL(experts, weights), src/llama-graph.cpp:990)
+// a tile launch's epilogue: the ADD_ID biases, the (oai) SwiGLU of a dual launch, the routing weight (MUL(experts, weights), src/llama-graph.cpp:990)
 struct mmq_moe_epi { const float * bias = nullptr; const float * bias2 = nullptr; size_t bias_stride = 0; const float * scale = nullptr; size_t scale_nb0 = 0, scale_nb1 = 0;
                      int oai = 0; float alpha = 0.0f, limit = 0.0f;
                      const float * glu_up = nullptr; size_t glu_up_nb1 = 0, glu_up_nb2 = 0; };     // (single-tensor launch as the gate half of a GLU: the finished up half, f32 [m, n_used, n_tokens])
-struct mmq_moe_plan { uint16_t * xb; int * table; int * table2; uint16_t * y16; size_t bytes; };     // table: 256-pair tiles (dual launch); table2: the down launch's tiles
-mmq_moe_plan mul_mat_q_id_plan(void * scratch, int64_t k, int64_t n_tokens, int64_t n_used, int64_t n_expert, int64_t m_glu);
-int    mul_mat_q_id_tile(int64_t n_used, int64_t n_tokens, int64_t n_expert);      // pairs per tile: 128 or 256
-void   mul_mat_q_id_sort(const int32_t * ids, size_t ids_nb0, size_t ids_nb1, int64_t n_used, int64_t n_tokens, int64_t n_expert, int tile, int * table, hipStream_t stream);
-void   mul_mat_q_id_act16(const float * b, size_t b_nb1, size_t b_nb2, int64_t k, int64_t n_b, int64_t n_tokens, uint16_t * xb, hipStream_t stream);
-void   mul_mat_q_id_tiles(int type_a, const void * W, const void * W2, size_t w_row_stride, size_t w_expert_stride, int64_t m, int64_t k,
-                          const uint16_t * xb, int64_t n_b, const int * table, int tile, int64_t n_used, int64_t n_tokens, int64_t n_expert,
-                          const mmq_moe_epi & epi, float * dst, size_t dst_nb1, size_t dst_nb2, uint16_t * y16, hipStream_t stream);
+// one launch over an expert stack. mul_mat_q_id (node by node: copy, sort, tiles) reads b / ids / scratch (mul_mat_q_id_scratch_bytes bytes) and sets xb / table / tile itself. mul_mat_q_id_tiles (the tiled
+// kernel over a sorted pair table) reads xb: bf16 rows [token][n_b][kp(k)] (n_b == 1: a row per token, n_used: per pair); W2 != NULL: the dual kernel (tile 256): GLU(W.x + bias, W2.x + bias2) -> dst (f32, may be NULL) and / or y16 (bf16 rows of m per pair)
+struct mmq_moe_call {
+    int type; const void * W; const void * W2; size_t w_row_stride, w_expert_stride; int64_t m, k, n_expert; int64_t n_used, n_tokens, n_b;      // the expert stack; the pairs
+    const float * b; size_t b_nb1, b_nb2; const int32_t * ids; size_t ids_nb0, ids_nb1; void * scratch;           // what the copy and the sort read and write
+    const uint16_t * xb; const int * table; int tile; mmq_moe_epi epi;
+    float * dst; size_t dst_nb1, dst_nb2; uint16_t * y16; hipStream_t stream;
+};
+void mul_mat_q_id(const mmq_moe_call & c);
+void mul_mat_q_id_tiles(const mmq_moe_call & c);
+// The fused expert chain of a prompt pass (backend_nodes.cpp try_fused_prefill_moe): one bf16 copy of the layer input and one sort serve gate, up and down. Planned once: the carve of
+// the scratch (table2: the down launch's tiles, when their size differs) and the form — dual: gate / up as ONE launch of 256-pair tiles, biases and (oai) SwiGLU in its epilogue; else the up
+// launch, then the gate launch, which reads the up product back (epi.glu_up). Both hand the down launch bf16 rows per pair (y16). dual_opt: option "moe_dual", or -1 (mmq.hip)
+struct mmq_moe_plan { uint16_t * xb; int * table; int * table2; uint16_t * y16; size_t bytes; bool dual; int tile, tile_down; };
+mmq_moe_plan mul_mat_q_id_plan(void * scratch, int64_t k, int64_t n_tokens, int64_t n_used, int64_t n_expert, int64_t m_glu, int dual_opt = -1);
+// copy, sort and the gate / up launch(es): c as for the dual launch (W = gate, W2 = up, epi.bias / bias2, b, ids); !pl.dual: epi.glu_up is the tensor the up launch writes.
+// Then (a second sort and) the down launch: reads pl.y16, adds its ADD_ID bias and multiplies with the routing weight; c: the down stack, ids, epi, dst
+void mul_mat_q_id_gate_up(const mmq_moe_call & c, const mmq_moe_plan & pl);
+void mul_mat_q_id_down(const mmq_moe_call & c, const mmq_moe_plan & pl);
 
 // ---- dense f16/f32 x f32 mat-mul with ggml broadcast (attention K.Q and V.KQ; tests/test-backend-ops.cpp:5791-5813)
 struct mm_dense_args {
@@ -188,10 +198,6 @@ void argsort(const tensor_desc & src, const tensor_desc & dst, int order, hipStr
 void unary(int op, const tensor_desc & src, const tensor_desc & dst, hipStream_t stream);
 void glu(int glu_op, bool swapped, const tensor_desc & a, const tensor_desc * b, const tensor_desc & dst, float alpha, float limit, hipStream_t stream);
 
-struct rope_params {
-    int n_dims, mode, n_ctx_orig;
-    float freq_base, freq_scale, ext_factor, attn_factor, beta_fast, beta_slow;
-};
 void rope(const tensor_desc & src, const int32_t * pos, const float * freq_factors, const tensor_desc & dst, const rope_params & p, hipStream_t stream);
 
 void soft_max(const tensor_desc & src, const tensor_desc * mask, const float * sinks, const tensor_desc & dst,
@@ -315,9 +321,6 @@ struct mmvq_group {
 // GLU launches only: the launch also writes its f32 output as the quantized image (act_q8 layout for n = 1) the next mat-vec reads;
 // counters: >= m/256 words, zero between launches (the kernel re-arms them). m % 256 == 0, one group, no expert stack.
 struct mmvq_fin { int kind; int pad; int8_t * qs; float * d; int16_t * bs; unsigned * counters; };
-// EPI_ROPE. table: n_dims/2 x (cos, sin) for the token at pos[0], filled by mul_mat_vec_q_fused_rope_table on the same stream before the launch
-// (one tiny launch per token and rope configuration instead of powf / cosf / sinf per row pair inside every norm+QKV launch)
-struct mmvq_rope { const int32_t * pos; const float * freq_factors; int head_dim; rope_params p; const float * table; };
 void mul_mat_vec_q_fused_rope_table(const mmvq_rope & rope, float * table, hipStream_t stream);
 
 // where the activation vector comes from

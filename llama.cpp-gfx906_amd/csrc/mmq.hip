@@ -1176,29 +1176,28 @@ __global__ void __launch_bounds__(256) k_combine(char * dst, size_t dst_nb1, con
     *(float4v *) (dst + (size_t) row*dst_nb1 + (size_t) c4*16) = a;
 }
 
-void mul_mat_q(int type_a, const void * W, size_t w_row_stride, int64_t m, int64_t k,
-               const float * x, size_t x_row_stride, int64_t n, void * scratch, bool scratch_ready, float * dst, size_t dst_col_stride_bytes,
-               const float * res, size_t res_row_stride, hipStream_t stream, mmq_deferred * defer) {
-    if (defer) *defer = {};
-    if (m == 0 || n == 0) return;
-    uint16_t * xb = (uint16_t *) scratch;
-    if (!scratch_ready) mmq_act_to_16<false>(x, x_row_stride, 0, 0, k, n, 1, 1, xb, stream);
-    const bool vec_ok = m % 4 == 0 && dst_col_stride_bytes % 16 == 0 && ((uintptr_t) dst % 16) == 0 && (!res || (res_row_stride % 16 == 0 && ((uintptr_t) res % 16) == 0));
-    const mmq_plan pl = mmq_plan_one(m, k, n, vec_ok);
-    const size_t planes_off = mul_mat_q_layout(k, n, m).planes_off;
-    float * planes = (float *) ((char *) scratch + planes_off);
-    mmq_args a = mmq_base_args(W, w_row_stride, 0, 0, m, k, xb, n, dst, dst_col_stride_bytes, 0, 0);
-    a.res = (const char *) res; a.res_nb1 = res_row_stride; a.ksplit = pl.ksplit;
+void mul_mat_q(const mmq_call & c) {
+    const mmq_act & x = c.act;
+    if (c.defer) *c.defer = {};
+    if (c.m == 0 || x.n == 0) return;
+    uint16_t * xb = (uint16_t *) x.scratch;
+    if (!x.scratch_ready) mmq_act_to_16<false>(x.x, x.x_row_stride, 0, 0, x.k, x.n, 1, 1, xb, c.stream);
+    const bool vec_ok = c.m % 4 == 0 && c.dst_stride % 16 == 0 && ((uintptr_t) c.dst % 16) == 0 && (!c.res || (c.res_stride % 16 == 0 && ((uintptr_t) c.res % 16) == 0));
+    const mmq_plan pl = mmq_plan_one(c.m, x.k, x.n, vec_ok);
+    const size_t planes_off = mul_mat_q_layout(x.k, x.n, c.m).planes_off;
+    float * planes = (float *) ((char *) x.scratch + planes_off);
+    mmq_args a = mmq_base_args(c.W, c.w_row_stride, 0, 0, c.m, x.k, xb, x.n, c.dst, c.dst_stride, 0, 0);
+    a.res = (const char *) c.res; a.res_nb1 = c.res_stride; a.ksplit = pl.ksplit;
     if (pl.ksplit > 1) a.dst2 = (char *) planes;
-    mmq_dispatch_type(type_a, "mmq", [&](auto t) {
+    mmq_dispatch_type(c.type, "mmq", [&](auto t) {
         constexpr int T_ = decltype(t)::value;
-        if (pl.tile == 256) launch_mmq_256<T_>(pl, a, stream);
-        else                hipLaunchKernelGGL((k_mmq<T_, 128>), pl.grid, dim3(256), MQ_LDS_BYTES, stream, a);
+        if (pl.tile == 256) launch_mmq_256<T_>(pl, a, c.stream);
+        else                hipLaunchKernelGGL((k_mmq<T_, 128>), pl.grid, dim3(256), MQ_LDS_BYTES, c.stream, a);
     });
-    if (defer && pl.ksplit > 1) { defer->np = pl.ksplit; defer->planes = planes; defer->planes_off = planes_off; return; }
-    const unsigned cgrid = (unsigned)((m/4*n + 255)/256);
-    if (pl.ksplit == 4)      hipLaunchKernelGGL(k_combine<4>, dim3(cgrid), dim3(256), 0, stream, (char *) dst, dst_col_stride_bytes, planes, (const char *) res, res_row_stride, m/4, n);
-    else if (pl.ksplit == 2) hipLaunchKernelGGL(k_combine<2>, dim3(cgrid), dim3(256), 0, stream, (char *) dst, dst_col_stride_bytes, planes, (const char *) res, res_row_stride, m/4, n);
+    if (c.defer && pl.ksplit > 1) { c.defer->np = pl.ksplit; c.defer->planes = planes; c.defer->planes_off = planes_off; return; }
+    const unsigned cgrid = (unsigned)((c.m/4*x.n + 255)/256);
+    if (pl.ksplit == 4)      hipLaunchKernelGGL(k_combine<4>, dim3(cgrid), dim3(256), 0, c.stream, (char *) c.dst, c.dst_stride, planes, (const char *) c.res, c.res_stride, c.m/4, x.n);
+    else if (pl.ksplit == 2) hipLaunchKernelGGL(k_combine<2>, dim3(cgrid), dim3(256), 0, c.stream, (char *) c.dst, c.dst_stride, planes, (const char *) c.res, c.res_stride, c.m/4, x.n);
 }
 
 // ---- several mat-muls on the same activations as one launch (wq / wk / wv of build_attn, src/llama-model.cpp:6017-6040) ----
@@ -1232,73 +1231,82 @@ __global__ void __launch_bounds__(256) k_combine_seg(const combine_seg_args p) {
     }
 }
 
-// false: not done (too few tiles for 256-token tiles, an unsupported mix of types, scratch too small) — the caller runs them one by one
-bool mul_mat_q_multi(int nseg, const int * types, const void * const * W, const size_t * w_row_stride, const int64_t * m, float * const * dst, const size_t * dst_stride,
-                     int64_t k, const float * x, size_t x_row_stride, int64_t n, void * scratch, size_t scratch_size, bool scratch_ready,
-                     const mmvq_rope * rope, const int * seg_rope, const mmq_kv_store * kvs, hipStream_t stream, const float * const * seg_bias) {
-    if (nseg < 2 || nseg > 3) return false;
-    if (rope) {        // heads of an even size that start at column multiples of 4
-        if (rope->head_dim % 4 != 0 || rope->p.n_dims % 2 != 0) return false;
-        for (int s = 0; s < nseg; s++) if (seg_rope[s] && m[s] % rope->head_dim != 0) return false;
+// what mul_mat_q_multi_takes and the launcher go by: the plan (ok: taken), the one or two weight types, what rides, the planes' place, the kernel's arguments but for rotation and planes
+struct mmq_multi_plan { mmq_plan pl; int t1, t2; bool rope, kv_store; mmq_layout lay; mmq_args a; };
+static mmq_multi_plan mmq_plan_call(const mmq_multi_call & c) {
+    mmq_multi_plan mp = {};
+    if (c.nseg < 2 || c.nseg > 3) return mp;
+    // what rides on the launch. (These were whole-launch arguments once — a rope descriptor, a table of stores, an array of bias rows — and the plan asked whether they were
+    // given; it now asks whether some segment uses one. The one caller never gave a descriptor, a table or an array that no segment used, so the answers are the same.)
+    bool bias = false;
+    for (int s = 0; s < c.nseg; s++) { mp.rope = mp.rope || c.seg[s].rope; mp.kv_store = mp.kv_store || c.seg[s].st_mode != 0; bias = bias || c.seg[s].bias != nullptr; }
+    if (mp.rope) {        // heads of an even size that start at column multiples of 4
+        if (c.rope.head_dim % 4 != 0 || c.rope.p.n_dims % 2 != 0) return mp;
+        for (int s = 0; s < c.nseg; s++) if (c.seg[s].rope && c.seg[s].m % c.rope.head_dim != 0) return mp;
     }
-    int t1 = types[0], t2 = types[0];
-    for (int s = 1; s < nseg; s++) if (types[s] != t1) { if (t2 != t1 && types[s] != t2) return false; t2 = types[s]; }
+    int & t1 = mp.t1 = c.seg[0].type, & t2 = mp.t2 = c.seg[0].type;
+    for (int s = 1; s < c.nseg; s++) if (c.seg[s].type != t1) { if (t2 != t1 && c.seg[s].type != t2) return mp; t2 = c.seg[s].type; }
     if (t1 != t2) {
         if (t1 == T_Q6_K) { const int t = t1; t1 = t2; t2 = t; }
-        if (!(t2 == T_Q6_K && (t1 == T_Q4_K || t1 == T_Q5_K))) return false;       // the mixed pairs of the K-quant mixes (attn_v one step up)
+        if (!(t2 == T_Q6_K && (t1 == T_Q4_K || t1 == T_Q5_K))) return mp;       // the mixed pairs of the K-quant mixes (attn_v one step up)
     }
-    mmq_args a = mmq_base_args(nullptr, 0, 0, 0, 0, k, (const uint16_t *) scratch, n, nullptr, 0, 0, 0);
-    a.nseg = nseg;
+    mmq_args & a = mp.a = mmq_base_args(nullptr, 0, 0, 0, 0, c.act.k, (const uint16_t *) c.act.scratch, c.act.n, nullptr, 0, 0, 0);
+    a.nseg = c.nseg;
     int64_t m_tot = 0; int tiles = 0; bool vec_ok = true;
-    for (int s = 0; s < nseg; s++) {
-        mmq_seg & g = a.seg[s];
-        g.W = (const char *) W[s]; g.dst = (char *) dst[s]; g.w_row_stride = w_row_stride[s]; g.dst_nb1 = dst_stride[s]; g.m = (int) m[s]; g.tile0 = tiles; g.col0 = (int) m_tot;
-        g.type2 = types[s] != t1 ? 1 : 0; g.rope = rope && seg_rope[s] ? 1 : 0; g.bias = seg_bias ? seg_bias[s] : nullptr;
-        vec_ok = vec_ok && m[s] % 4 == 0 && dst_stride[s] % 16 == 0 && ((uintptr_t) dst[s] % 16) == 0;
-        m_tot += m[s]; tiles += (int)((m[s] + MQ_BM - 1)/MQ_BM);
+    for (int s = 0; s < c.nseg; s++) {
+        const mmq_multi_seg & cs = c.seg[s]; mmq_seg & g = a.seg[s];
+        g.W = (const char *) cs.W; g.dst = (char *) cs.dst; g.w_row_stride = cs.w_row_stride; g.dst_nb1 = cs.dst_stride; g.m = (int) cs.m; g.tile0 = tiles; g.col0 = (int) m_tot;
+        g.type2 = cs.type != t1 ? 1 : 0; g.rope = cs.rope ? 1 : 0; g.bias = cs.bias;
+        vec_ok = vec_ok && cs.m % 4 == 0 && cs.dst_stride % 16 == 0 && ((uintptr_t) cs.dst % 16) == 0;
+        m_tot += cs.m; tiles += (int)((cs.m + MQ_BM - 1)/MQ_BM);
     }
-    if (nseg < 3) a.seg[2] = a.seg[1];
-    if (rope) a.rope = make_fused_rope(*rope);
-    const mmq_plan pl = mmq_plan_multi(m_tot, tiles, k, n, vec_ok, rope != nullptr, kvs != nullptr, seg_bias != nullptr);
-    if (!pl.ok) return false;
-    const mmq_layout lay = mul_mat_q_layout(k, n, m_tot, pl.ksplit > 1 ? pl.ksplit : 0);
-    if (lay.total > scratch_size) return false;
-    a.m = (int) m_tot; a.mtiles = tiles; a.ksplit = pl.ksplit;
-    if (!scratch_ready) mmq_act_to_16<false>(x, x_row_stride, 0, 0, k, n, 1, 1, (uint16_t *) scratch, stream);
-    float * planes = (float *) ((char *) scratch + lay.planes_off);
+    if (c.nseg < 3) a.seg[2] = a.seg[1];
+    mp.pl = mmq_plan_multi(m_tot, tiles, c.act.k, c.act.n, vec_ok, mp.rope, mp.kv_store, bias);
+    if (!mp.pl.ok) return mp;
+    mp.lay = mul_mat_q_layout(c.act.k, c.act.n, m_tot, mp.pl.ksplit > 1 ? mp.pl.ksplit : 0);
+    mp.pl.ok = mp.lay.total <= c.act.scratch_size;
+    a.m = (int) m_tot; a.mtiles = tiles; a.ksplit = mp.pl.ksplit;
+    return mp;
+}
+bool mul_mat_q_multi_takes(const mmq_multi_call & c) { return mmq_plan_call(c).pl.ok; }
+void mul_mat_q_multi(const mmq_multi_call & c) {
+    mmq_multi_plan mp = mmq_plan_call(c);
+    if (!mp.pl.ok) { fprintf(stderr, "mmq_multi: called on a launch that mul_mat_q_multi_takes refuses\n"); abort(); }
+    const mmq_plan & pl = mp.pl; const mmq_act & x = c.act; mmq_args & a = mp.a;
+    if (mp.rope) a.rope = make_fused_rope(c.rope);
+    if (!x.scratch_ready) mmq_act_to_16<false>(x.x, x.x_row_stride, 0, 0, x.k, x.n, 1, 1, (uint16_t *) x.scratch, c.stream);
+    float * planes = (float *) ((char *) x.scratch + mp.lay.planes_off);
     if (pl.ksplit > 1) a.dst2 = (char *) planes;
-    if (t1 != t2) {
-        if (t1 == T_Q4_K) launch_mmq_256<T_Q4_K, T_Q6_K>(pl, a, stream); else launch_mmq_256<T_Q5_K, T_Q6_K>(pl, a, stream);
-    } else mmq_dispatch_type(t1, "mmq_multi", [&](auto t) { launch_mmq_256<decltype(t)::value>(pl, a, stream); });
+    if (mp.t1 != mp.t2) {
+        if (mp.t1 == T_Q4_K) launch_mmq_256<T_Q4_K, T_Q6_K>(pl, a, c.stream); else launch_mmq_256<T_Q5_K, T_Q6_K>(pl, a, c.stream);
+    } else mmq_dispatch_type(mp.t1, "mmq_multi", [&](auto t) { launch_mmq_256<decltype(t)::value>(pl, a, c.stream); });
     if (pl.ksplit > 1) {
         combine_seg_args ca{};
-        ca.planes = planes; ca.m4_tot = m_tot/4; ca.n = n; ca.nseg = nseg; ca.rope = a.rope;
-        if (kvs) for (int s = 0; s < nseg; s++) { ca.st16[s] = kvs->st16[s]; ca.st_idx[s] = kvs->st_idx[s]; ca.st_row_elems[s] = kvs->st_row_elems[s]; ca.st_mode[s] = kvs->st_mode[s]; ca.m_seg[s] = (int) m[s]; }
-        for (int s = 0; s < 3; s++) { const int q = s < nseg ? s : nseg - 1; ca.dst[s] = a.seg[q].dst; ca.dst_nb1[s] = a.seg[q].dst_nb1; ca.col4[s] = a.seg[q].col0/4; ca.rope_seg[s] = a.seg[q].rope; }
-        const unsigned cgrid = (unsigned)((m_tot/4*n + 255)/256);
-        if (pl.ksplit == 4) hipLaunchKernelGGL(k_combine_seg<4>, dim3(cgrid), dim3(256), 0, stream, ca);
-        else                hipLaunchKernelGGL(k_combine_seg<2>, dim3(cgrid), dim3(256), 0, stream, ca);
+        ca.planes = planes; ca.m4_tot = a.m/4; ca.n = x.n; ca.nseg = c.nseg; ca.rope = a.rope;
+        if (mp.kv_store) for (int s = 0; s < c.nseg; s++) { ca.st16[s] = c.seg[s].st16; ca.st_idx[s] = c.seg[s].st_idx; ca.st_row_elems[s] = c.seg[s].st_row_elems; ca.st_mode[s] = c.seg[s].st_mode; ca.m_seg[s] = (int) c.seg[s].m; }
+        for (int s = 0; s < 3; s++) { const int q = s < c.nseg ? s : c.nseg - 1; ca.dst[s] = a.seg[q].dst; ca.dst_nb1[s] = a.seg[q].dst_nb1; ca.col4[s] = a.seg[q].col0/4; ca.rope_seg[s] = a.seg[q].rope; }
+        const unsigned cgrid = (unsigned)((a.m/4*(int64_t) x.n + 255)/256);
+        if (pl.ksplit == 4) hipLaunchKernelGGL(k_combine_seg<4>, dim3(cgrid), dim3(256), 0, c.stream, ca);
+        else                hipLaunchKernelGGL(k_combine_seg<2>, dim3(cgrid), dim3(256), 0, c.stream, ca);
     }
-    return true;
 }
 
 // gate / up + SwiGLU of build_ffn (src/llama-graph.cpp:632-774) for many tokens: dst[n][m] = silu(Wg.x) * (Wu.x)
 bool mul_mat_q_glu_supported(int64_t m, int64_t n) { return mmq_plan_glu(m, n).ok; }
-void mul_mat_q_glu(int type_a, const void * Wg, const void * Wu, size_t w_row_stride, int64_t m, int64_t k,
-                   const float * x, size_t x_row_stride, int64_t n, void * scratch, bool scratch_ready, float * dst, size_t dst_col_stride_bytes, hipStream_t stream,
-                   uint16_t * y16) {
-    if (m == 0 || n == 0) return;
-    uint16_t * xb = (uint16_t *) scratch;
-    if (!scratch_ready) mmq_act_to_16<false>(x, x_row_stride, 0, 0, k, n, 1, 1, xb, stream);
-    const mmq_plan pl = mmq_plan_glu(m, n);
-    mmq_args a = mmq_base_args(Wg, w_row_stride, 0, 0, m, k, xb, n, dst, dst_col_stride_bytes, 0, 0);
-    a.W2 = (const char *) Wu; a.y16 = y16;
+void mul_mat_q_glu(const mmq_call & c) {
+    const mmq_act & x = c.act;
+    if (c.m == 0 || x.n == 0) return;
+    uint16_t * xb = (uint16_t *) x.scratch;
+    if (!x.scratch_ready) mmq_act_to_16<false>(x.x, x.x_row_stride, 0, 0, x.k, x.n, 1, 1, xb, c.stream);
+    const mmq_plan pl = mmq_plan_glu(c.m, x.n);
+    mmq_args a = mmq_base_args(c.W, c.w_row_stride, 0, 0, c.m, x.k, xb, x.n, c.dst, c.dst_stride, 0, 0);
+    a.W2 = (const char *) c.W2; a.y16 = c.y16;
     { static const int dbg = (int) env_int("GGML_MI355X_MMQ_DBG", 0); a.dbg = dbg; }
-    mmq_dispatch_type(type_a, "mmq_glu", [&](auto t) {
+    mmq_dispatch_type(c.type, "mmq_glu", [&](auto t) {
         constexpr int T_ = decltype(t)::value;
         // the wave-specialized kernel where its producers' four register stages fit (Q4_K, MXFP4: 168 registers, no scratch; the other formats' raw blocks are larger and spill)
-        if constexpr (T_ == T_Q4_K || T_ == T_MXFP4) if (mmq_ws_on()) { mmq_launch<k_mmq_ws<T_, 256, true>>(pl.grid, 768, MQ_LDS_BYTES_WS256, a, stream); return; }
-        mmq_launch<k_mmq<T_, 256, true>>(pl.grid, 512, MQ_LDS_BYTES_DUAL, a, stream);
+        if constexpr (T_ == T_Q4_K || T_ == T_MXFP4) if (mmq_ws_on()) { mmq_launch<k_mmq_ws<T_, 256, true>>(pl.grid, 768, MQ_LDS_BYTES_WS256, a, c.stream); return; }
+        mmq_launch<k_mmq<T_, 256, true>>(pl.grid, 512, MQ_LDS_BYTES_DUAL, a, c.stream);
     });
 }
 
@@ -1340,8 +1348,15 @@ bool mul_mat_q_id_supported(int64_t n_expert, int64_t n_used, int64_t n_tokens) 
 size_t mul_mat_q_id_scratch_bytes(int64_t k, int64_t n_b, int64_t n_tokens, int64_t n_used, int64_t n_expert) {
     return mul_mat_q_layout(k, n_b*n_tokens, 0).x_end + moe_table_bytes(n_used*n_tokens, n_expert) + 256;
 }
+static int moe_tile(int64_t n_used, int64_t n_tokens, int64_t n_expert) {      // pairs per tile of a single-tensor launch: 128 or 256
+    static const int forced = (int) env_int("GGML_MI355X_MOE_TILE", 0);
+    if (forced == 128 || forced == 256) return forced;
+    // measured at 512 tokens: Mixtral (~128 pairs per expert, every wave of a tile multiplies): 128-pair tiles 9.85k tok/s, 256-pair tiles on the 16-wave kernel 7.9k
+    // (on k_mmq<256> 6.97k); gpt-oss (64 pairs per expert: a quarter of the 16-wave kernel's waves multiply, all sixteen decode): 256-pair tiles 22.85k, 128-pair 21.7k
+    return n_used*n_tokens <= 96*n_expert ? 256 : 128;
+}
 // the fused expert chain (gate / up / GLU -> down): bf16 copy of the layer input | tile table | tile table 2 | bf16 GLU result, one row per (token, slot) pair
-mmq_moe_plan mul_mat_q_id_plan(void * scratch, int64_t k, int64_t n_tokens, int64_t n_used, int64_t n_expert, int64_t m_glu) {
+mmq_moe_plan mul_mat_q_id_plan(void * scratch, int64_t k, int64_t n_tokens, int64_t n_used, int64_t n_expert, int64_t m_glu, int dual_opt) {
     const size_t x_end = mul_mat_q_layout(k, n_tokens, 0).x_end, table_bytes = moe_table_bytes(n_used*n_tokens, n_expert);
     mmq_moe_plan pl;
     pl.xb = (uint16_t *) scratch;
@@ -1349,56 +1364,66 @@ mmq_moe_plan mul_mat_q_id_plan(void * scratch, int64_t k, int64_t n_tokens, int6
     pl.table2 = (int *) ((char *) pl.table + table_bytes);
     pl.y16 = (uint16_t *) ((char *) pl.table2 + table_bytes);
     pl.bytes = x_end + 2*table_bytes + (((size_t) n_used*n_tokens*mmq_kp(m_glu)*2 + 255) & ~(size_t) 255) + 256;
+    // Few pairs per expert (gpt-oss at 512 tokens: 64): the dual kernel — one 256-pair tile per expert, eight decoding waves, both tensors against one activation tile
+    // (pp512 18.7k -> 22.2k tok/s). Many (Mixtral: ~128): the dual kernel's single workgroup per CU decodes at half the rate of two 128-pair workgroups (926 us against
+    // 2 x 350 - 390 + 62 for the GLU kernel), so the two products stay separate launches of the 128-pair kernel: the up launch writes its tensor, the gate launch reads
+    // it back in its epilogue and evaluates the GLU there. The same rule as moe_tile's.
+    static const int dual_env = (int) env_int("GGML_MI355X_MOE_DUAL", -1);
+    if (dual_opt < 0) dual_opt = dual_env;
+    pl.dual = dual_opt >= 0 ? dual_opt != 0 : n_used*n_tokens <= 96*n_expert;
+    pl.tile_down = moe_tile(n_used, n_tokens, n_expert); pl.tile = pl.dual ? 256 : pl.tile_down;
     return pl;
 }
-int mul_mat_q_id_tile(int64_t n_used, int64_t n_tokens, int64_t n_expert) {
-    static const int forced = (int) env_int("GGML_MI355X_MOE_TILE", 0);
-    if (forced == 128 || forced == 256) return forced;
-    // measured at 512 tokens: Mixtral (~128 pairs per expert, every wave of a tile multiplies): 128-pair tiles 9.85k tok/s, 256-pair tiles on the 16-wave kernel 7.9k
-    // (on k_mmq<256> 6.97k); gpt-oss (64 pairs per expert: a quarter of the 16-wave kernel's waves multiply, all sixteen decode): 256-pair tiles 22.85k, 128-pair 21.7k
-    return n_used*n_tokens <= 96*n_expert ? 256 : 128;
+static void moe_sort(const mmq_moe_call & c, int tile, int * table) {
+    moe_sort_args ps = { (const char *) c.ids, c.ids_nb0, c.ids_nb1, (int) c.n_used, (int) c.n_tokens, (int) c.n_expert, moe_max_tiles(c.n_used*c.n_tokens, c.n_expert), table, tile };
+    hipLaunchKernelGGL(k_moe_sort, dim3(1), dim3(256), 0, c.stream, ps);
 }
-void mul_mat_q_id_sort(const int32_t * ids, size_t ids_nb0, size_t ids_nb1, int64_t n_used, int64_t n_tokens, int64_t n_expert, int tile, int * table, hipStream_t stream) {
-    moe_sort_args ps = { (const char *) ids, ids_nb0, ids_nb1, (int) n_used, (int) n_tokens, (int) n_expert, moe_max_tiles(n_used*n_tokens, n_expert), table, tile };
-    hipLaunchKernelGGL(k_moe_sort, dim3(1), dim3(256), 0, stream, ps);
-}
-void mul_mat_q_id_act16(const float * b, size_t b_nb1, size_t b_nb2, int64_t k, int64_t n_b, int64_t n_tokens, uint16_t * xb, hipStream_t stream) {
-    mmq_act_to_16<false>(b, b_nb1, b_nb2, 0, k, n_b, n_tokens, 1, xb, stream);     // dense [token][n_b][k] bf16
-}
-
-// the tiled kernel over a sorted pair table. xb: bf16 rows [token][n_b][kp(k)] (n_b == 1: every slot of a token reads the token's row; n_b == n_used: a row per pair);
-// W2 != NULL: the dual kernel (tile must be 256): GLU(W.x + bias, W2.x + bias2) -> dst (f32, may be NULL) and / or y16 (bf16 rows of m per pair)
-void mul_mat_q_id_tiles(int type_a, const void * W, const void * W2, size_t w_row_stride, size_t w_expert_stride, int64_t m, int64_t k,
-                        const uint16_t * xb, int64_t n_b, const int * table, int tile, int64_t n_used, int64_t n_tokens, int64_t n_expert,
-                        const mmq_moe_epi & epi, float * dst, size_t dst_nb1, size_t dst_nb2, uint16_t * y16, hipStream_t stream) {
-    if (m == 0 || n_used*n_tokens == 0) return;
-    if (W2 && tile != 256) { fprintf(stderr, "mmq_id: the dual kernel runs 256-pair tiles\n"); abort(); }
-    mmq_args a = mmq_base_args(W, w_row_stride, w_expert_stride, 0, m, k, xb, n_used*n_tokens, dst, dst_nb1, dst_nb2, 0);
-    a.y16 = y16; a.W2 = (const char *) W2;
-    a.moe = table; a.moe_max_tiles = moe_max_tiles(n_used*n_tokens, n_expert); a.n_used = (int) n_used; a.n_b = (int) n_b;
-    a.bias = epi.bias; a.bias2 = epi.bias2; a.bias_stride = epi.bias_stride; a.scale = epi.scale; a.scale_nb0 = epi.scale_nb0; a.scale_nb1 = epi.scale_nb1;
+static void moe_act16(const mmq_moe_call & c, uint16_t * xb) { mmq_act_to_16<false>(c.b, c.b_nb1, c.b_nb2, 0, c.k, c.n_b, c.n_tokens, 1, xb, c.stream); }     // dense [token][n_b][k] bf16
+void mul_mat_q_id_tiles(const mmq_moe_call & c) {
+    if (c.m == 0 || c.n_used*c.n_tokens == 0) return;
+    if (c.W2 && c.tile != 256) { fprintf(stderr, "mmq_id: the dual kernel runs 256-pair tiles\n"); abort(); }
+    mmq_args a = mmq_base_args(c.W, c.w_row_stride, c.w_expert_stride, 0, c.m, c.k, c.xb, c.n_used*c.n_tokens, c.dst, c.dst_nb1, c.dst_nb2, 0);
+    a.y16 = c.y16; a.W2 = (const char *) c.W2;
+    a.moe = c.table; a.moe_max_tiles = moe_max_tiles(c.n_used*c.n_tokens, c.n_expert); a.n_used = (int) c.n_used; a.n_b = (int) c.n_b;
+    const mmq_moe_epi & epi = c.epi; a.bias = epi.bias; a.bias2 = epi.bias2; a.bias_stride = epi.bias_stride; a.scale = epi.scale; a.scale_nb0 = epi.scale_nb0; a.scale_nb1 = epi.scale_nb1;
     a.glu_oai = epi.oai; a.glu_alpha = epi.alpha; a.glu_limit = epi.limit;
     a.glu_up = (const char *) epi.glu_up; a.glu_up_nb1 = epi.glu_up_nb1; a.glu_up_nb2 = epi.glu_up_nb2;
     const dim3 grid((unsigned) a.moe_max_tiles, (unsigned) a.mtiles, 1);
-    mmq_dispatch_type(type_a, "mmq_id", [&](auto t) {
+    mmq_dispatch_type(c.type, "mmq_id", [&](auto t) {
         constexpr int T_ = decltype(t)::value;
-        if (W2)               mmq_launch<k_mmq<T_, 256, true, T_, true>>(grid, 512, MQ_LDS_BYTES_DUAL, a, stream);
-        else if (tile == 256) mmq_launch<k_mmq16<T_, T_, true>>(grid, 1024, MQ_LDS_BYTES_256, a, stream);
-        else                  mmq_launch<k_mmq<T_, 128, false, T_, true>>(grid, 256, MQ_LDS_BYTES, a, stream);
+        if (c.W2)               mmq_launch<k_mmq<T_, 256, true, T_, true>>(grid, 512, MQ_LDS_BYTES_DUAL, a, c.stream);
+        else if (c.tile == 256) mmq_launch<k_mmq16<T_, T_, true>>(grid, 1024, MQ_LDS_BYTES_256, a, c.stream);
+        else                    mmq_launch<k_mmq<T_, 128, false, T_, true>>(grid, 256, MQ_LDS_BYTES, a, c.stream);
     });
 }
-
-void mul_mat_q_id(int type_a, const void * W, size_t w_row_stride, size_t w_expert_stride, int64_t m, int64_t k,
-                  const float * b, size_t b_nb1, size_t b_nb2, int64_t n_b,
-                  const int32_t * ids, size_t ids_nb0, size_t ids_nb1, int64_t n_used, int64_t n_tokens, int64_t n_expert,
-                  void * scratch, float * dst, size_t dst_nb1, size_t dst_nb2, hipStream_t stream) {
-    if (m == 0 || n_used*n_tokens == 0) return;
-    uint16_t * xb = (uint16_t *) scratch;      // bf16 copy of the input | tile table, as mul_mat_q_id_scratch_bytes sizes them
-    int * table = (int *) ((char *) scratch + mul_mat_q_layout(k, n_b*n_tokens, 0).x_end);
-    const int tile = mul_mat_q_id_tile(n_used, n_tokens, n_expert);
-    mul_mat_q_id_act16(b, b_nb1, b_nb2, k, n_b, n_tokens, xb, stream);
-    mul_mat_q_id_sort(ids, ids_nb0, ids_nb1, n_used, n_tokens, n_expert, tile, table, stream);
-    mul_mat_q_id_tiles(type_a, W, nullptr, w_row_stride, w_expert_stride, m, k, xb, n_b, table, tile, n_used, n_tokens, n_expert, mmq_moe_epi{}, dst, dst_nb1, dst_nb2, nullptr, stream);
+void mul_mat_q_id(const mmq_moe_call & c) {
+    if (c.m == 0 || c.n_used*c.n_tokens == 0) return;
+    uint16_t * xb = (uint16_t *) c.scratch;      // bf16 copy of the input | tile table, as mul_mat_q_id_scratch_bytes sizes them
+    int * table = (int *) ((char *) c.scratch + mul_mat_q_layout(c.k, c.n_b*c.n_tokens, 0).x_end);
+    mmq_moe_call t = c;
+    t.xb = xb; t.table = table; t.tile = moe_tile(c.n_used, c.n_tokens, c.n_expert);
+    moe_act16(c, xb);
+    moe_sort(c, t.tile, table);
+    mul_mat_q_id_tiles(t);
+}
+void mul_mat_q_id_gate_up(const mmq_moe_call & c, const mmq_moe_plan & pl) {
+    mmq_moe_call g = c, u = c;
+    g.n_b = u.n_b = 1; g.xb = u.xb = pl.xb; g.table = u.table = pl.table; g.tile = u.tile = pl.tile;
+    moe_act16(g, pl.xb);
+    moe_sort(g, pl.tile, pl.table);
+    if (!pl.dual) {      // the up launch: its product (+ bias) into the tensor the gate launch reads back
+        u.W = c.W2; u.W2 = nullptr; u.epi = mmq_moe_epi{}; u.epi.bias = c.epi.bias2; u.epi.bias_stride = c.epi.bias_stride;
+        u.dst = const_cast<float *>(c.epi.glu_up); u.dst_nb1 = c.epi.glu_up_nb1; u.dst_nb2 = c.epi.glu_up_nb2; u.y16 = nullptr;
+        mul_mat_q_id_tiles(u);
+        g.W2 = nullptr; g.epi.bias2 = nullptr;
+    }
+    mul_mat_q_id_tiles(g);
+}
+void mul_mat_q_id_down(const mmq_moe_call & c, const mmq_moe_plan & pl) {
+    mmq_moe_call d = c;
+    d.n_b = c.n_used; d.xb = pl.y16; d.tile = pl.tile_down; d.table = pl.tile_down != pl.tile ? pl.table2 : pl.table;
+    if (pl.tile_down != pl.tile) moe_sort(c, pl.tile_down, pl.table2);
+    mul_mat_q_id_tiles(d);
 }
 
 // f16 x f32 with ggml broadcast on the matrix cores (n > 8 columns): a rows contiguous f16, b rows contiguous f32
@@ -1416,6 +1441,35 @@ void mul_mat_dense_mfma(const mm_dense_args & p, void * scratch, hipStream_t str
     a.ne12 = (int) p.ne12; a.r2 = (int)(p.ne12/p.ne02); a.r3 = (int)(p.ne13/p.ne03);
     const dim3 grid((unsigned)((p.ne11 + MQ_BN - 1)/MQ_BN), (unsigned) a.mtiles, (unsigned)(p.ne12*p.ne13));
     hipLaunchKernelGGL((k_mmq<T_F16>), grid, dim3(256), MQ_LDS_BYTES, stream, a);
+}
+
+// diagnostic export (no device needed; tests/test_prefill_plan_table.py): what the host code decides about a prefill launch, from shapes alone. Every answer starts
+// with ok / takes; a launch that is not taken reports zeros behind it.
+//   form 0, one tensor:   in = m, k, n, vec_ok                                               out = ok, tile, ksplit, grid.x, grid.y, w16
+//   form 1, grouped:      in = nseg, type[3], m[3], k, n, vec_ok, head_dim, kv, bias, scratch_bytes    out = takes, tile, ksplit, grid.x, grid.y, w16
+//                         (head_dim > 0: segments 0 and 1 carry the rotation; kv: the last two segments a row and an element store; bias: segment 0 a bias row)
+//   form 2, gate / up:    in = m, n                                                          out = ok
+//   form 3, expert chain: in = k, n_tokens, n_used, n_expert, m, dual_opt                    out = 1, dual, tile, tile_down, bytes
+extern "C" void mi355x_prefill_plan_info(int form, const int64_t * in, int64_t * out) {
+    auto put = [&](const mmq_plan & pl) {
+        for (int i = 0; i < 6; i++) out[i] = 0;
+        if (pl.ok) { out[0] = 1; out[1] = pl.tile; out[2] = pl.ksplit; out[3] = pl.grid.x; out[4] = pl.grid.y; out[5] = pl.w16; }
+    };
+    if (form == 0) put(mmq_plan_one(in[0], in[1], in[2], in[3] != 0));
+    else if (form == 1) {
+        static const float some_bias = 0.0f;      // (an address: never read)
+        mmq_multi_call c = {};
+        c.nseg = (int) in[0]; c.act.k = in[7]; c.act.n = in[8]; c.act.scratch_size = (size_t) in[13];
+        for (int s = 0; s < 3 && s < c.nseg; s++) { c.seg[s].type = (int) in[1 + s]; c.seg[s].m = in[4 + s]; c.seg[s].dst_stride = in[9] ? 16 : 4; }
+        if (in[10] > 0) { c.rope.head_dim = (int) in[10]; c.rope.p.n_dims = (int) in[10]; c.seg[0].rope = c.seg[1].rope = true; }
+        if (in[11] && c.nseg >= 2 && c.nseg <= 3) { c.seg[c.nseg - 2].st_mode = 1; c.seg[c.nseg - 1].st_mode = 2; }
+        if (in[12]) c.seg[0].bias = &some_bias;
+        put(mmq_plan_call(c).pl);
+    } else if (form == 2) out[0] = mul_mat_q_glu_supported(in[0], in[1]);
+    else if (form == 3) {
+        const mmq_moe_plan pl = mul_mat_q_id_plan(nullptr, in[0], in[1], in[2], in[3], in[4], (int) in[5]);
+        out[0] = 1; out[1] = pl.dual; out[2] = pl.tile; out[3] = pl.tile_down; out[4] = (int64_t) pl.bytes;
+    }
 }
 
 } // namespace mi355x

@@ -441,6 +441,41 @@ def test_prompt_pass_qkv_with_bias_rows(name, k):
         assert np.array_equal(outs[1][q], outs[0][q]), (q, orc.nmse(outs[0][q], outs[1][q]))
 
 
+def test_prompt_pass_qkv_with_bias_rows_on_a_split_k():
+    """The one fall-back of try_fused_prefill_qkv: bias rows on a grouped launch whose k splits. q4_K, k = 2048, rows (4096, 512, 512), 512 tokens: 40 m-tiles x 2 token
+    tiles = 80 tiles, so k splits in two and the launcher does not take the bias rows (they ride on the epilogue only). The matcher then takes the plain grouped launch
+    and runs the three ADDs behind it. Against the exact product: the bound of test_prefill_qkv_group, the same launch form. Against fusion off: the same bits (measured on
+    the commit before the launchers took call records: the one-by-one launches split this k in two as well, and the planes and the bias are added in the same order)."""
+    rng = np.random.default_rng(32)
+    qt = QTYPES["q4_K"]; n = 512; k = 2048; ms = (4096, 512, 512)
+    ws = [orc.random_blocks(rng, qt, (m,), k) for m in ms]
+    bs = [rng.uniform(-1, 1, size=(1, 1, 1, m)).astype(np.float32) for m in ms]
+    x_ = rng.uniform(-1, 1, size=(1, 1, n, k)).astype(np.float32)
+    be = backend(); outs = {}
+    for fusion in (1, 0):
+        be.set_option("fusion", fusion)
+        with gg.Context() as ctx:
+            x = ctx.new_tensor(gg.F32, (k, n))
+            wt = [ctx.new_tensor(qt, (k, m)) for m in ms]; bt = [ctx.new_tensor(gg.F32, (m,)) for m in ms]
+            o = [L.ggml_add(ctx.ctx, L.ggml_mul_mat(ctx.ctx, w, x), b) for w, b in zip(wt, bt)]
+            gf = gg.graph_of(ctx, *o)
+            assert ctx.alloc(be)
+            for t, a in list(zip(wt, ws)) + list(zip(bt, bs)) + [(x, x_)]: gg.tensor_set(t, a)
+            be.reset_counters(); be.compute(gf)
+            outs[fusion] = [gg.tensor_get(t)[0, 0].copy() for t in o]
+            if fusion:
+                cnt = be.counters()
+                assert cnt["mmq_launches"] == 1, cnt
+                # the value the commit before the launchers took call records gives for this graph (run there once): the bf16 copy of x, the grouped launch, three ADDs
+                # (the pass that combines the two planes is not counted: DESIGN.md §6)
+                assert cnt["kernels_launched"] == 5, cnt
+    be.set_option("fusion", 1)
+    for q in range(3):
+        exp = orc.dequantize(ws[q], qt).astype(np.float64) @ x_[0, 0].astype(np.float64).T + bs[q][0, 0, 0][:, None].astype(np.float64)
+        assert orc.nmse(exp.T, outs[1][q]) <= 2e-5, (q, orc.nmse(exp.T, outs[1][q]))
+        assert np.array_equal(outs[1][q], outs[0][q]), (q, orc.nmse(outs[0][q], outs[1][q]))
+
+
 @pytest.mark.parametrize("n_used,with_res", [(2, True), (4, True), (4, False), (8, True)])
 def test_moe_slot_sum_many_tokens(n_used, with_res):
     """The end of build_moe_ffn for a prompt pass (src/llama-graph.cpp:996-1012 + the residual ADD of src/llama-model.cpp:6096): the ADD chain over the slot views of
