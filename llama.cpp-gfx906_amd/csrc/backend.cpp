@@ -511,6 +511,8 @@ static bool mi_supports_op(const struct ggml_tensor * op) {
             return s0->type == GGML_TYPE_F32;
         case GGML_OP_CPY: case GGML_OP_CONT: case GGML_OP_DUP: {
             const enum ggml_type st = s0->type, dt = op->op == GGML_OP_CPY ? s1->type : op->type;
+            // a quantized KV cache's shift and defrag (src/llama-kv-cache-unified.cpp:1416-1670): CPY only, F32 <-> Q8_0 / Q4_0 and a move within one of the two types
+            if (ggml_is_quantized(st) || ggml_is_quantized(dt)) return op->op == GGML_OP_CPY && cpy_quantized_supported(desc(s0), desc(s1));
             return (float_type(st) && float_type(dt)) || (st == GGML_TYPE_I32 && dt == GGML_TYPE_I32);
         }
         case GGML_OP_SET_ROWS:

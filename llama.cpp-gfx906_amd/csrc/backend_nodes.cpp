@@ -634,6 +634,28 @@ static int try_fused_kv_store(mi_backend_ctx * c, struct ggml_cgraph * g, int i)
     return j - i + 1;
 }
 
+// CPY(kv -> F32) -> ROPE -> CPY(F32 -> kv): the K-shift of a Q8_0 / Q4_0 cache (build_rope_shift, src/llama-kv-cache-unified.cpp:1416-1452: ggml_cast,
+// ggml_rope_ext, ggml_cpy back into the same view) as one in-place launch. The last node must write exactly what the first read (placement, type, shape,
+// strides) and nobody else may read the two F32 tensors; anything else runs node by node. ggml_cast names its result as its own src[1]: that use is not a reader.
+static int try_fused_kv_shift(mi_backend_ctx * c, struct ggml_cgraph * g, int i) {
+    const struct ggml_tensor * cast = g->nodes[i];
+    const struct ggml_tensor * kv = cast->src[0];
+    const int j1 = next_real(g, i), j2 = j1 > 0 ? next_real(g, j1) : -1;
+    if (j2 < 0) return 0;
+    const struct ggml_tensor * rp = g->nodes[j1]; const struct ggml_tensor * back = g->nodes[j2];
+    if (rp->op != GGML_OP_ROPE || rp->src[0] != cast || rp->type != GGML_TYPE_F32 || !ggml_are_same_shape(rp, cast) || rp->src[1]->type != GGML_TYPE_I32) return 0;
+    if (back->op != GGML_OP_CPY || back->src[0] != rp) return 0;
+    const struct ggml_tensor * to = back->src[1];
+    if (to->data != kv->data || to->type != kv->type || !ggml_are_same_shape(to, kv) || !ggml_are_same_shape(kv, cast) ||
+        to->nb[0] != kv->nb[0] || to->nb[1] != kv->nb[1] || to->nb[2] != kv->nb[2] || to->nb[3] != kv->nb[3]) return 0;
+    if (cast->src[1] != cast || n_uses(c, cast) != 2 || (cast->flags & GGML_TENSOR_FLAG_OUTPUT) || !is_internal(c, rp)) return 0;      // (2: itself and the ROPE)
+    const rope_params p = rope_params_of(rp);
+    if (!kv_shift_supported(desc(kv), p) || ggml_nelements(rp->src[1]) < kv->ne[2]) return 0;
+    kv_shift(desc(kv), (const int32_t *) rp->src[1]->data, rp->src[2] ? (const float *) rp->src[2]->data : nullptr, p, c->stream);
+    c->cnt.kernels_launched++;
+    return j2 - i + 1;
+}
+
 // MUL_MAT(k, q) -> SOFT_MAX -> MUL_MAT(v, kq) -> PERMUTE -> CONT (src/llama-graph.cpp:1283-1330). With per-sequence KV streams every tensor of the chain has
 // ne[3] = n_stream (q [hd, T, n_head, n_stream], :1231-1238; the mask [n_kv, T_pad, 1, n_stream]) and the CONT's rows are stream-major: token t of stream s is
 // row s*T + t. One launch either way; a chain in which only some of the tensors carry streams is left to the single nodes.
@@ -1377,6 +1399,7 @@ int compute_node(mi_backend_ctx * c, struct ggml_cgraph * g, int i) {
         else if (node->op == GGML_OP_MUL_MAT_ID) { consumed = try_fused_moe_experts(c, g, i); if (!consumed) consumed = try_fused_prefill_moe(c, g, i); }
         else if (node->op == GGML_OP_ADD && s0 && s0->view_src) consumed = try_fused_slot_sum(c, g, i);
         else if (node->op == GGML_OP_RMS_NORM) { consumed = try_fused_norm(c, g, i); if (!consumed) pp_flush(c); }
+        else if (node->op == GGML_OP_CPY && node->type == GGML_TYPE_F32 && (s0->type == GGML_TYPE_Q8_0 || s0->type == GGML_TYPE_Q4_0)) consumed = try_fused_kv_shift(c, g, i);
     }
     if (!consumed) {
         consumed = 1;

@@ -4,6 +4,7 @@
 // reductions, no LDS beyond a 4-float cross-wave exchange.
 #include "dev_common.h"
 #include "kernels.h"
+#include "kv_quant_dev.h"
 
 #include <math.h>
 
@@ -264,9 +265,63 @@ __global__ void __launch_bounds__(256) k_cpy(const td src, const td dst, int64_t
         st_elem(dp, dst.type, ld_elem(sp, src.type));
     }
 }
+// a Q8_0 / Q4_0 side (a quantized KV cache: ggml_cast and ggml_cpy in build_rope_shift, the view-to-view moves of build_graph_defrag —
+// src/llama-kv-cache-unified.cpp:1416-1670): one thread per 32-element block. ne0 is the same on both sides and whole blocks, a quantized side's
+// rows are whole blocks (nb0 = the type's size); block ib of row r, rows counted in each tensor's own ne1..ne3 order.
+// DIR 0: f32 -> q (kv_quant_dev.h's row quantizers, any f32 strides); 1: q -> f32; 2: q -> q of one type, the block's bytes as 16-bit words
+template <int TYPE, int DIR>
+__global__ void __launch_bounds__(256) k_cpy_q(const td src, const td dst, int64_t n_blocks) {
+    const int64_t i = (int64_t) blockIdx.x*256 + threadIdx.x;
+    if (i >= n_blocks) return;
+    const int64_t nb0 = src.ne0/32;
+    const idx4 sx = unravel(i, nb0, src.ne1, src.ne2), dx = unravel(i, nb0, dst.ne1, dst.ne2);
+    const int64_t ib = sx.i0;
+    const char * sp = src.data + sx.i1*src.nb1 + sx.i2*src.nb2 + sx.i3*src.nb3;
+    char * dp = dst.data + dx.i1*dst.nb1 + dx.i2*dst.nb2 + dx.i3*dst.nb3;
+    constexpr int BB = kv_block_bytes<TYPE>();
+    if (DIR == 2) {
+        const u16_u * a = (const u16_u *) (sp + ib*BB); u16_u * b = (u16_u *) (dp + ib*BB);
+        uint16_t w[BB/2];
+#pragma unroll
+        for (int j = 0; j < BB/2; j++) w[j] = a[j].v;
+#pragma unroll
+        for (int j = 0; j < BB/2; j++) b[j].v = w[j];
+        return;
+    }
+    if (DIR == 0) {
+        float v[32];
+#pragma unroll
+        for (int j = 0; j < 32; j++) v[j] = *(const float *) (sp + (ib*32 + j)*src.nb0);
+        quant_block<TYPE>(v, dp + ib*BB);
+    } else {
+#pragma unroll
+        for (int j = 0; j < 32; j++) *(float *) (dp + (ib*32 + j)*dst.nb0) = dequant_elem<TYPE>(sp, ib*32 + j);
+    }
+}
+template <int TYPE>
+static void cpy_q(int dir, const tensor_desc & src, const tensor_desc & dst, int64_t n_blocks, hipStream_t stream) {
+    const dim3 g((unsigned)((n_blocks + 255)/256)), b(256);
+    if (dir == 0)      hipLaunchKernelGGL((k_cpy_q<TYPE, 0>), g, b, 0, stream, mk(src), mk(dst), n_blocks);
+    else if (dir == 1) hipLaunchKernelGGL((k_cpy_q<TYPE, 1>), g, b, 0, stream, mk(src), mk(dst), n_blocks);
+    else               hipLaunchKernelGGL((k_cpy_q<TYPE, 2>), g, b, 0, stream, mk(src), mk(dst), n_blocks);
+}
+bool cpy_quantized_supported(const tensor_desc & src, const tensor_desc & dst) {
+    const bool sq = src.type == T_Q8_0 || src.type == T_Q4_0, dq = dst.type == T_Q8_0 || dst.type == T_Q4_0;
+    if (!((sq && dst.type == T_F32) || (dq && src.type == T_F32) || (sq && src.type == dst.type))) return false;
+    if (src.ne[0] != dst.ne[0] || src.ne[0] % 32 != 0 || src.ne[0]*src.ne[1]*src.ne[2]*src.ne[3] != dst.ne[0]*dst.ne[1]*dst.ne[2]*dst.ne[3]) return false;
+    if (sq && src.nb[0] != (size_t) weight_format_of(src.type).bytes) return false;
+    if (dq && dst.nb[0] != (size_t) weight_format_of(dst.type).bytes) return false;
+    return true;
+}
 void cpy(const tensor_desc & src, const tensor_desc & dst, hipStream_t stream) {
     const int64_t n = src.ne[0]*src.ne[1]*src.ne[2]*src.ne[3];
     if (n == 0) return;
+    const bool sq = src.type == T_Q8_0 || src.type == T_Q4_0, dq = dst.type == T_Q8_0 || dst.type == T_Q4_0;
+    if (sq || dq) {
+        const int dir = sq && dq ? 2 : (sq ? 1 : 0);
+        if ((sq ? src.type : dst.type) == T_Q8_0) cpy_q<T_Q8_0>(dir, src, dst, n/32, stream); else cpy_q<T_Q4_0>(dir, src, dst, n/32, stream);
+        return;
+    }
     hipLaunchKernelGGL(k_cpy, dim3((unsigned)((n + 255)/256)), dim3(256), 0, stream, mk(src), mk(dst), n);
 }
 
@@ -281,8 +336,7 @@ __global__ void __launch_bounds__(256) k_set_rows(const td src, const td idx, co
     st_elem(dst.data + i0*dst.nb0 + r*dst.nb1 + i2*dst.nb2 + i3*dst.nb3, dst.type, v);
 }
 // quantized destination (a quantized KV cache: -ctk q8_0 / q4_0; tests/test-backend-ops.cpp:5333-5343): one thread per 32-element
-// block, the reference row quantizers restated operation for operation (gguf-py/gguf/quants.py:222-238 Q4_0, :381-393 Q8_0 —
-// oracle/ggml_oracle.c quantize_row_q4_0_ref / quantize_row_q8_0_ref, pinned bit-exactly by tests/golden/quant_*.npz)
+// block, through the row quantizers of kv_quant_dev.h
 template <int TYPE>
 __global__ void __launch_bounds__(256) k_set_rows_q(const td src, const td idx, const td dst, int64_t n_blocks) {
     const int64_t i = (int64_t) blockIdx.x*256 + threadIdx.x;
@@ -294,34 +348,7 @@ __global__ void __launch_bounds__(256) k_set_rows_q(const td src, const td idx, 
     float v[32];
 #pragma unroll
     for (int j = 0; j < 32; j++) v[j] = *(const float *) (x + j*src.nb0);
-    uint8_t * out = (uint8_t *) (dst.data + r*dst.nb1 + i2*dst.nb2 + i3*dst.nb3) + ib*(TYPE == T_Q8_0 ? 34 : 18);
-    if (TYPE == T_Q8_0) {
-        float amax = 0.0f;
-#pragma unroll
-        for (int j = 0; j < 32; j++) { const float a = fabsf(v[j]); if (a > amax) amax = a; }
-        const float d = amax/127.0f;
-        const float id = d != 0.0f ? 1.0f/d : 0.0f;
-        const uint16_t dh = f32_to_f16_bits(d);
-        out[0] = (uint8_t) dh; out[1] = (uint8_t)(dh >> 8);
-#pragma unroll
-        for (int j = 0; j < 32; j++) out[2 + j] = (uint8_t)(int8_t) roundf(v[j]*id);
-    } else {
-        float amax = 0.0f, mx = 0.0f;
-#pragma unroll
-        for (int j = 0; j < 32; j++) { if (amax < fabsf(v[j])) { amax = fabsf(v[j]); mx = v[j]; } }
-        float d = mx/-8.0f;
-        // keep the product in a register of its own: fused into the f16 conversion (v_fma_mixlo_f16 with a +0 addend) a zero block's
-        // d = 0 / -8 = -0.0 came out as +0.0, one bit off the reference's bytes
-        asm volatile("" : "+v"(d));
-        const float id = d != 0.0f ? 1.0f/d : 0.0f;
-        const uint16_t dh = f32_to_f16_bits(d);
-        out[0] = (uint8_t) dh; out[1] = (uint8_t)(dh >> 8);
-#pragma unroll
-        for (int j = 0; j < 16; j++) {
-            const int v0 = (int)(v[j]*id + 8.5f), v1 = (int)(v[16 + j]*id + 8.5f);
-            out[2 + j] = (uint8_t)((v0 < 15 ? v0 : 15) | ((v1 < 15 ? v1 : 15) << 4));
-        }
-    }
+    quant_block<TYPE>(v, dst.data + r*dst.nb1 + i2*dst.nb2 + i3*dst.nb3 + ib*kv_block_bytes<TYPE>());
 }
 void set_rows(const tensor_desc & src, const tensor_desc & idx, const tensor_desc & dst, hipStream_t stream) {
     const int64_t n = src.ne[0]*src.ne[1]*src.ne[2]*src.ne[3];
@@ -511,6 +538,18 @@ static __device__ __forceinline__ void rope_yarn(float theta_extrap, float freq_
     s = sinf(theta)*mscale;
 }
 
+// (cos, sin)*mscale of pair ip (elements 2*ip, 2*ip + 1 in NORM mode; ip, ip + n_dims/2 in NEOX) at position pos, and the rotation by it:
+// the arithmetic of k_rope and of k_kv_shift, which must leave the same bits
+static __device__ __forceinline__ void rope_cs(int32_t pos, int64_t ip, const float * ff, const rope_params & p, rope_corr cd, float theta_scale, float & c, float & s) {
+    const float theta_base = (float) pos*powf(theta_scale, (float) ip);
+    const float freq_factor = ff ? ff[ip] : 1.0f;
+    rope_yarn(theta_base/freq_factor, p.freq_scale, cd, 2*ip, p.ext_factor, p.attn_factor, c, s);
+}
+static __device__ __forceinline__ void rope_rotate(float x0, float x1, float c, float s, float & y0, float & y1) {
+    y0 = x0*c - x1*s;
+    y1 = x0*s + x1*c;
+}
+
 // one thread per rotated pair; src/dst [ne0 = head dim, ne1 = heads, ne2 = tokens, ne3]
 template <bool NEOX>
 __global__ void __launch_bounds__(256) k_rope(const td src, const int32_t * pos, const float * ff, const td dst, rope_params p, rope_corr cd,
@@ -527,31 +566,98 @@ __global__ void __launch_bounds__(256) k_rope(const td src, const int32_t * pos,
         st_elem(y + (i0 + 1)*dst.nb0, dst.type, ld_elem(x + (i0 + 1)*src.nb0, src.type));
         return;
     }
-    const float theta_base = (float) pos[i2]*powf(theta_scale, (float) ip);
-    const float freq_factor = ff ? ff[ip] : 1.0f;
     float c, s;
-    rope_yarn(theta_base/freq_factor, p.freq_scale, cd, i0, p.ext_factor, p.attn_factor, c, s);
+    rope_cs(pos[i2], ip, ff, p, cd, theta_scale, c, s);
     const int64_t ia = NEOX ? ip : i0, ib = NEOX ? ip + p.n_dims/2 : i0 + 1;
     const float x0 = ld_elem(x + ia*src.nb0, src.type), x1 = ld_elem(x + ib*src.nb0, src.type);
-    st_elem(y + ia*dst.nb0, dst.type, x0*c - x1*s);
-    st_elem(y + ib*dst.nb0, dst.type, x0*s + x1*c);
+    float y0, y1;
+    rope_rotate(x0, x1, c, s, y0, y1);
+    st_elem(y + ia*dst.nb0, dst.type, y0);
+    st_elem(y + ib*dst.nb0, dst.type, y1);
 }
 
 static float rope_corr_dim(int n_dims, int n_ctx_orig, float n_rot, float base) {
     return n_dims*logf(n_ctx_orig/(n_rot*2*(float) M_PI))/(2*logf(base));
 }
-void rope(const tensor_desc & src, const int32_t * pos, const float * freq_factors, const tensor_desc & dst, const rope_params & p, hipStream_t stream) {
-    const int64_t npairs = (src.ne[0]/2)*src.ne[1]*src.ne[2]*src.ne[3];
-    if (npairs == 0) return;
-    const float theta_scale = powf(p.freq_base, -2.0f/p.n_dims);
+static rope_corr rope_corr_of(const rope_params & p) {
     rope_corr cd;
     const float start = floorf(rope_corr_dim(p.n_dims, p.n_ctx_orig, p.beta_fast, p.freq_base));
     const float end   = ceilf (rope_corr_dim(p.n_dims, p.n_ctx_orig, p.beta_slow, p.freq_base));
     cd.lo = fmaxf(0.0f, start);
     cd.hi = fminf((float)(p.n_dims - 1), end);
+    return cd;
+}
+void rope(const tensor_desc & src, const int32_t * pos, const float * freq_factors, const tensor_desc & dst, const rope_params & p, hipStream_t stream) {
+    const int64_t npairs = (src.ne[0]/2)*src.ne[1]*src.ne[2]*src.ne[3];
+    if (npairs == 0) return;
+    const float theta_scale = powf(p.freq_base, -2.0f/p.n_dims);
+    const rope_corr cd = rope_corr_of(p);
     const dim3 g((unsigned)((npairs + 255)/256));
     if (p.mode & 2) hipLaunchKernelGGL((k_rope<true>),  g, dim3(256), 0, stream, mk(src), pos, freq_factors, mk(dst), p, cd, theta_scale, npairs);
     else            hipLaunchKernelGGL((k_rope<false>), g, dim3(256), 0, stream, mk(src), pos, freq_factors, mk(dst), p, cd, theta_scale, npairs);
+}
+
+// ---- the K-shift of a quantized cache in place — src/llama-kv-cache-unified.cpp:1416-1526 (build_rope_shift: ggml_cast(k, F32) -> ggml_rope_ext ->
+// ggml_cpy(tmp, k)) as ONE launch over kv [ne0 = head dim, ne1 = kv heads, ne2 = cells, ne3], Q8_0 / Q4_0 rows of whole blocks. A workgroup takes a few
+// (head, cell) rows: phase one, one thread per pair, dequantizes (kv_quant_dev.h) and rotates (rope_cs / rope_rotate, as k_rope) into LDS as f32, elements
+// from n_dims on unchanged; after the barrier phase two, one thread per block, runs the row quantizer from LDS and writes the block back. The row is the
+// unit because NEOX partners i and i + n_dims/2 sit in different blocks of it; it is read completely before any of it is written and nothing is read
+// across rows, so the launch is safe in place. Same device functions on the same f32 values as CPY(q -> F32), ROPE, CPY(F32 -> q): the same bytes.
+// LDS: element e of the workgroup's rows at e + e/32 (phase two's threads read 32 floats each, 32 apart: the pad spreads them over the banks)
+constexpr int KV_SHIFT_ELEMS = 2048;       // f32 elements a workgroup holds (rows of up to KV_SHIFT_MAX_HD; at least one row)
+constexpr int KV_SHIFT_MAX_HD = 8192;
+template <int TYPE, bool NEOX>
+__global__ void __launch_bounds__(256) k_kv_shift(const td kv, const int32_t * pos, const float * ff, rope_params p, rope_corr cd, float theta_scale,
+                                                  int64_t n_rows, int rows_per_wg) {
+    extern __shared__ float kv_rows[];
+    const int hd = (int) kv.ne0, half = hd/2, nblk_row = hd/32;
+    const int64_t row0 = (int64_t) blockIdx.x*rows_per_wg;
+    const int nr = (int)(n_rows - row0 < rows_per_wg ? n_rows - row0 : rows_per_wg);
+    for (int q = threadIdx.x; q < nr*half; q += 256) {
+        const int rl = q/half, ip = q - rl*half;
+        const idx4 rx = unravel(row0 + rl, kv.ne1, kv.ne2, 1ll << 30); const int64_t i1 = rx.i0, i2 = rx.i1, i3 = rx.i2;
+        const char * x = kv.data + i1*kv.nb1 + i2*kv.nb2 + i3*kv.nb3;
+        const int i0 = 2*ip, base = rl*hd;
+        int ia = i0, ib = i0 + 1;
+        float y0, y1;
+        if (i0 >= p.n_dims) {   // pass-through for dims beyond n_dims
+            y0 = dequant_elem<TYPE>(x, ia); y1 = dequant_elem<TYPE>(x, ib);
+        } else {
+            float c, s;
+            rope_cs(pos[i2], ip, ff, p, cd, theta_scale, c, s);
+            if (NEOX) { ia = ip; ib = ip + p.n_dims/2; }
+            rope_rotate(dequant_elem<TYPE>(x, ia), dequant_elem<TYPE>(x, ib), c, s, y0, y1);
+        }
+        kv_rows[base + ia + ((base + ia) >> 5)] = y0;
+        kv_rows[base + ib + ((base + ib) >> 5)] = y1;
+    }
+    __syncthreads();
+    for (int b = threadIdx.x; b < nr*nblk_row; b += 256) {
+        const int rl = b/nblk_row, ib = b - rl*nblk_row;
+        const idx4 rx = unravel(row0 + rl, kv.ne1, kv.ne2, 1ll << 30); const int64_t i1 = rx.i0, i2 = rx.i1, i3 = rx.i2;
+        float v[32];
+#pragma unroll
+        for (int j = 0; j < 32; j++) v[j] = kv_rows[b*33 + j];
+        quant_block<TYPE>(v, kv.data + i1*kv.nb1 + i2*kv.nb2 + i3*kv.nb3 + (int64_t) ib*kv_block_bytes<TYPE>());
+    }
+}
+bool kv_shift_supported(const tensor_desc & kv, const rope_params & p) {
+    return (kv.type == T_Q8_0 || kv.type == T_Q4_0) && kv.nb[0] == (size_t) weight_format_of(kv.type).bytes && kv.ne[0] % 32 == 0 && kv.ne[0] > 0 && kv.ne[0] <= KV_SHIFT_MAX_HD &&
+           (p.mode & ~2) == 0 && p.n_dims % 2 == 0 && p.n_dims >= 0 && p.n_dims <= kv.ne[0] && kv.ne[1]*kv.ne[2]*kv.ne[3] < (1ll << 31);
+}
+void kv_shift(const tensor_desc & kv, const int32_t * pos, const float * freq_factors, const rope_params & p, hipStream_t stream) {
+    const int64_t n_rows = kv.ne[1]*kv.ne[2]*kv.ne[3];
+    if (n_rows == 0) return;
+    const float theta_scale = powf(p.freq_base, -2.0f/p.n_dims);
+    const rope_corr cd = rope_corr_of(p);
+    const int rows_per_wg = KV_SHIFT_ELEMS/(int) kv.ne[0] > 0 ? KV_SHIFT_ELEMS/(int) kv.ne[0] : 1;
+    const int elems = rows_per_wg*(int) kv.ne[0];
+    const dim3 g((unsigned)((n_rows + rows_per_wg - 1)/rows_per_wg));
+    const size_t lds = (size_t)(elems + elems/32)*4;
+#define MI_KVS(T_, N_) hipLaunchKernelGGL((k_kv_shift<T_, N_>), g, dim3(256), lds, stream, mk(kv), pos, freq_factors, p, cd, theta_scale, n_rows, rows_per_wg)
+    if (kv.type == T_Q8_0) { if (p.mode & 2) MI_KVS(T_Q8_0, true); else MI_KVS(T_Q8_0, false); }
+    else                   { if (p.mode & 2) MI_KVS(T_Q4_0, true); else MI_KVS(T_Q4_0, false); }
+#undef MI_KVS
 }
 
 // ---- SOFT_MAX ext — src/llama-graph.cpp:1312-1313; tests/test-backend-ops.cpp:3569-3626 (NMSE 1e-6) -------

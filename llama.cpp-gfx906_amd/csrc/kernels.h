@@ -175,7 +175,9 @@ enum bin_op { BIN_ADD = 0, BIN_MUL = 1, BIN_DIV = 2, BIN_SUB = 3 };
 void bin_bcast(int op, const tensor_desc & a, const tensor_desc & b, const tensor_desc & dst, hipStream_t stream);
 void add_id(const tensor_desc & a, const tensor_desc & bias, const tensor_desc & ids, const tensor_desc & dst, hipStream_t stream);
 void scale(const tensor_desc & src, const tensor_desc & dst, float s, float b, hipStream_t stream);
-void cpy(const tensor_desc & src, const tensor_desc & dst, hipStream_t stream);      // f32<->f16/f32 strided copy/convert (CPY, CONT, DUP)
+void cpy(const tensor_desc & src, const tensor_desc & dst, hipStream_t stream);      // f32<->f16/f32 strided copy/convert (CPY, CONT, DUP); CPY with a Q8_0 / Q4_0 side
+// CPY with a quantized side: F32 -> Q8_0 / Q4_0, Q8_0 / Q4_0 -> F32, Q8_0 -> Q8_0, Q4_0 -> Q4_0; the same ne0 on both sides, whole blocks, quantized rows dense
+bool cpy_quantized_supported(const tensor_desc & src, const tensor_desc & dst);
 void set_rows(const tensor_desc & src, const tensor_desc & idx, const tensor_desc & dst, hipStream_t stream);
 void get_rows(const tensor_desc & src, const tensor_desc & idx, const tensor_desc & dst, hipStream_t stream);
 void sum_rows(const tensor_desc & src, const tensor_desc & dst, hipStream_t stream);
@@ -199,6 +201,10 @@ void unary(int op, const tensor_desc & src, const tensor_desc & dst, hipStream_t
 void glu(int glu_op, bool swapped, const tensor_desc & a, const tensor_desc * b, const tensor_desc & dst, float alpha, float limit, hipStream_t stream);
 
 void rope(const tensor_desc & src, const int32_t * pos, const float * freq_factors, const tensor_desc & dst, const rope_params & p, hipStream_t stream);
+// CPY(kv -> F32) -> ROPE -> CPY(F32 -> kv) on a Q8_0 / Q4_0 cache view [head dim, kv heads, cells, ne3] in place, one launch (elem.hip: k_kv_shift);
+// pos: one I32 per cell (ne2). The bytes are those the three launches leave.
+bool kv_shift_supported(const tensor_desc & kv, const rope_params & p);
+void kv_shift(const tensor_desc & kv, const int32_t * pos, const float * freq_factors, const rope_params & p, hipStream_t stream);
 
 void soft_max(const tensor_desc & src, const tensor_desc * mask, const float * sinks, const tensor_desc & dst,
               float scale, float max_bias, hipStream_t stream);
